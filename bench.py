@@ -115,7 +115,13 @@ def parse(argv=None):
     ap.add_argument("--generate-cpu-baseline", action="store_true",
                     help="also time the reference's sampling schedule on the host cores (bounded sample, extrapolated)")
     ap.add_argument("--cpu-seconds", type=float, default=24.0, help="budget of the CPU baseline samples (whole run)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): the "
+                         "losses it returned and a fixed seeded sample of the model state it left behind (see dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -245,6 +251,43 @@ def roofline_block(es, mode, traffic_file, kernel_note):
                             "separate passes of this command, profiles/%s); algorithmic flops per launch = %.3e"
                             % (src, es["flops_per_launch"]),
             "kernel": kernel_note, "peak_note": PEAK_NOTE[mode], "per_kind": es["per_kind"]}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed, for comparing two builds output for output
+# ---------------------------------------------------------------------------------------------------------------------
+DUMP_STATE_SAMPLE = 1 << 22        # elements per model state sample: 16 MB of float32 each
+DUMP_SEED = 20240607
+
+
+def _state_sample(model, n, seed):
+    """Every floating-point entry of model.state_dict() (the reference's key layout), in key order, flattened into one
+    vector; when that is longer than n, the n elements at a fixed seeded set of positions (sorted)."""
+    sd = model.state_dict()
+    flat = torch.cat([sd[k].detach().reshape(-1).float() for k in sorted(sd) if sd[k].is_floating_point()])
+    if flat.numel() > n:
+        pos = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(seed))[:n].sort().values
+        flat = flat[pos.to(flat.device)]
+    return flat.cpu().numpy()
+
+
+def dump_outputs(path, losses, ds_loss, vq, ds):
+    """What the last timed step computed, as DIR/<name>.npy in float32 (about 32 MB in all): the losses the step returns
+    (vqvae_<key> of its last VQ-VAE train step, dsfvt_loss_cross_entropy) and, after its optimizer updates, a sample of each
+    model's state (vqvae_state_sample, dsfvt_state_sample: _state_sample, DUMP_STATE_SAMPLE elements at most).  The
+    inputs, the initial weights and the sample positions are seeded, so two runs with the same arguments can be compared
+    output for output.  -> {name: shape}."""
+    import numpy as np
+    arrays = {"vqvae_%s" % k: v.detach().float().cpu().numpy() for k, v in losses.items()}
+    arrays["dsfvt_loss_cross_entropy"] = ds_loss.detach().float().cpu().numpy()
+    arrays["vqvae_state_sample"] = _state_sample(vq.model, DUMP_STATE_SAMPLE, DUMP_SEED)
+    arrays["dsfvt_state_sample"] = _state_sample(ds.model, DUMP_STATE_SAMPLE, DUMP_SEED + 1)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -817,6 +860,8 @@ def run(args):
 
     # Pass 1 -- the timed region: exactly K steps, nothing but the product path between the two barriers.
     elapsed, stats, (losses, ds_loss) = timed_steps(step, args.steps, args.warmup, world, device)
+    # what the last timed step computed, before pass 2 trains the models further
+    dumped = dump_outputs(args.dump_outputs, losses, ds_loss, vq, ds) if args.dump_outputs and rank == 0 else None
     # Pass 2 -- the same K steps again with a HIP event pair around every engine launch (on the launch stream).
     timer, instrumented_ms = instrumented(step, args.steps, args.warmup + args.steps)
     math_mode = L.get_math_mode()
@@ -920,6 +965,8 @@ def run(args):
         }
         if parity is not None:
             out["parity"] = parity
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
         out["extra"] = extra
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, gate_state)

@@ -286,6 +286,37 @@ def test_bench_self_launches_one_rank_per_gpu():
     assert r.returncode != 0 and "WORLD_SIZE=2 but --gpus 1" in (r.stderr + r.stdout)
 
 
+def test_bench_dump_outputs_on_toy_models(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR` (bench.dump_outputs) on two toy models on CPU: the returned losses and every floating
+    state entry in key order as float32 .npy files; above the sample size a seeded sample that is the same from call to
+    call; `--steps` below 1 is refused."""
+    import types
+    import numpy as np
+    import bench
+    torch.manual_seed(0)
+    vq = types.SimpleNamespace(model=torch.nn.Linear(3, 2))
+    ds = types.SimpleNamespace(model=torch.nn.Sequential(torch.nn.Linear(40, 50), torch.nn.Linear(50, 4)))
+    vq.model.register_buffer("steps", torch.tensor(7))                             # integer entries are not state samples
+    losses = {"loss_reconstruction": torch.tensor(0.25, requires_grad=True), "loss_commitment": torch.tensor(0.5)}
+    monkeypatch.setattr(bench, "DUMP_STATE_SAMPLE", 1000)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), losses, torch.tensor(6.5), vq, ds)
+    assert shapes == {"vqvae_loss_reconstruction": [], "vqvae_loss_commitment": [], "dsfvt_loss_cross_entropy": [],
+                      "vqvae_state_sample": [8], "dsfvt_state_sample": [1000]}
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in shapes}
+    assert all(x.dtype == np.float32 for x in a.values())
+    assert float(a["vqvae_loss_reconstruction"]) == 0.25 and float(a["dsfvt_loss_cross_entropy"]) == 6.5
+    sd = vq.model.state_dict()
+    assert np.array_equal(a["vqvae_state_sample"], torch.cat([sd["bias"], sd["weight"].reshape(-1)]).numpy())
+    full = torch.cat([v.reshape(-1) for _, v in sorted(ds.model.state_dict().items())]).numpy()
+    assert np.isin(a["dsfvt_state_sample"], full).all() and len(np.unique(a["dsfvt_state_sample"])) > 990
+    bench.dump_outputs(str(tmp_path / "b"), losses, torch.tensor(6.5), vq, ds)
+    for n in shapes:
+        assert np.array_equal(a[n], np.load(tmp_path / "b" / (n + ".npy"))), n
+    assert bench.parse(["--steps", "3", "--dump-outputs", "d"]).dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
 def test_relu_decision_matching_helper_on_a_toy_network():
     """tests/util_relu.py (the gradient comparison that is exact about ReLU units sitting on their threshold) on a two-layer
     network with one planted undecided unit: a gradient that differs from fp64 only through that unit's decision is accepted

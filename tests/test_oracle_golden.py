@@ -201,8 +201,15 @@ def test_g9_pieces(golden, vtp):
     y, wm = O.masked_conv3d(vtp["decoder.conv.conv.weight"], vtp["decoder.conv.conv.bias"], g["x"])
     assert rel_err(y, g["masked_conv_out"]) < FTOL
     assert torch.equal(wm[:4, :4], g["masked_taps"])
-    assert torch.equal(O.positional_encoding_table(512, 1, 16, 16), g["pos_table"])
-    assert torch.equal(O.positional_encoding_table(48, 3, 4, 5), g["pos_table_48_345"])
+    # sin / cos / exp come from the host's math library (MKL picks its code path by CPU vendor), which is faithful to about an
+    # ulp but not bit-identical from host to host: the tables of the reference and of the oracle built on another CPU differ
+    # by a few ulps of 1.  Bit for bit, the oracle's table is the product's (lvt_amd PositionalEncoding) on this host.
+    from lvt_amd.modeling.autoregressive.vt_attention import PositionalEncoding
+    for args, key in (((512, 1, 16, 16), "pos_table"), ((48, 3, 4, 5), "pos_table_48_345")):
+        tab = O.positional_encoding_table(*args)
+        d, T, H, W = args
+        assert torch.equal(tab, PositionalEncoding(d).table(T, H, W, "cpu").t().reshape(d, T, H, W)), key
+        assert float((tab - g[key]).abs().max()) <= 4 * 2.0 ** -24, key
     pre = "decoder.block_local_attention.0."
     B = O.rel_position_bias(vtp[pre + "dt_bank"], vtp[pre + "dh_bank"], vtp[pre + "dw_bank"], (1, 16, 16))
     assert torch.equal(B[3, 0], g["B_dec0_head3"])
@@ -224,7 +231,12 @@ def test_g10_block_local_attention(golden, vtp, tag, pre, masked):
     assert rel_err(p[pre + "mha.proj.weight"].grad[:8], g["grad_proj_rows"]) < 1e-4
     assert rel_err(p[pre + "dh_bank"].grad, g["grad_dh_bank"]) < 1e-4
     assert rel_err(p[pre + "dw_bank"].grad, g["grad_dw_bank"]) < 1e-4
-    assert rel_err(p[pre + "dt_bank"].grad, g["grad_dt_bank"]) < 1e-3
+    # a (1, 16, 16) block has one time offset: the dt bank adds one constant per head to every logit of a row, which the
+    # softmax cancels -- its gradient is exactly 0 (as test_g15_g17 notes for t == 1), and what the reference and the oracle
+    # return is fp32 roundoff, whose digits differ from host to host; both must be roundoff next to the dh / dw banks'
+    scale = max(float(p[pre + "dh_bank"].grad.abs().max()), float(p[pre + "dw_bank"].grad.abs().max()))
+    assert float(p[pre + "dt_bank"].grad.abs().max()) < 1e-5 * scale
+    assert float(g["grad_dt_bank"].abs().max()) < 1e-5 * scale
     assert rel_err(p[pre + "mha.layer_norm.weight"].grad, g["grad_ln_w"]) < 1e-4
     assert rel_err(p[pre + "ffn.1.weight"].grad[:8], g["grad_ffn1_rows"]) < 1e-4
     assert rel_err(p[pre + "ffn.3.bias"].grad, g["grad_ffn3_b"]) < 1e-4
@@ -379,13 +391,26 @@ def test_g15_g17_variant_loss_and_grads(golden, tag):
     norms = torch.tensor([float(p[n].grad.norm()) for n in names], dtype=torch.float64)
     ref = g["grad_norms"].double()
     assert float(((norms - ref).abs() / (ref + 1e-6)).max()) < 1e-3
-    assert rel_err(p["encoder.conv.weight"].grad[:2], g["grad_enc_conv_rows"]) < 1e-4
-    assert rel_err(p["encoder.slice_embedding.weight"].grad, g["grad_slice_emb"]) < 1e-4
+    # These gradients come out of heavy cancellation: in DSSVT / DSTSVT fp32 holds them only to 1e-4 .. 1.2e-3 of their size,
+    # the reference's own capture included, so two fp32 evaluations agree to 1e-4 only when they round alike -- which another
+    # CPU's BLAS does not.  The arbiter is the oracle in fp64: the captured reference must match it (an error in the formula
+    # is O(1)), and the fp32 oracle must be as accurate as the reference's fp32 run (1e-4 where fp32 does better).
+    p64 = {k: v.double().requires_grad_(True) for k, v in params.items()}
+    O.vt_supervised_loss(p64, ctx, sl, si, ig, class_idx=cls, **geo)[0].backward()
+
+    def near(part, key):
+        exact = part(p64)
+        ref_err = rel_err(g[key], exact)
+        assert ref_err < 2e-3, (key, ref_err)
+        assert rel_err(part(p), exact) < max(1e-4, 2 * ref_err), key
+
+    near(lambda q: q["encoder.conv.weight"].grad[:2], "grad_enc_conv_rows")
+    near(lambda q: q["encoder.slice_embedding.weight"].grad, "grad_slice_emb")
     if VARIANTS[tag]["block"][0] > 1:      # for t == 1 the bank is a per-head constant shift: gradient exactly 0
-        assert rel_err(p["decoder.block_local_attention.3.dt_bank"].grad, g["grad_dec3_dt"]) < 1e-4
-    assert rel_err(p["encoder.linear_projector.weight"].grad[:4, :, 0, 0, 0], g["grad_enc_proj_rows"]) < 1e-4
+        near(lambda q: q["decoder.block_local_attention.3.dt_bank"].grad, "grad_dec3_dt")
+    near(lambda q: q["encoder.linear_projector.weight"].grad[:4, :, 0, 0, 0], "grad_enc_proj_rows")
     if cls is not None:
-        assert rel_err(p["encoder.class_embedding.weight"].grad, g["grad_class_emb"]) < 1e-4
+        near(lambda q: q["encoder.class_embedding.weight"].grad, "grad_class_emb")
 
 
 def test_g15_block_split_entire_video_logits(golden):

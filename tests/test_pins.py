@@ -5,6 +5,7 @@
 * f2 loader records + `latent_video_paths.npy` cache (reference data/datasets/latents.py:10-40) and the mapper fed
   with such a record (dataset_mapper.py:68-77, 113-149) -- fixture G20.
 """
+import math
 import os
 import random
 
@@ -32,14 +33,23 @@ def _cfg(path):
     return cfg
 
 
+PIN_THREADS = 8     # intra-op threads of the run that captured G19 (its _meta): the rounding of a float64 sum depends on
+                    # how the threads split it, so the checksums are summed the same way on a host with more cores
+
+
 def _pins(state_dict):
     names, rows = [], []
-    for k, v in state_dict.items():
-        if not v.dtype.is_floating_point:
-            continue
-        d = v.detach().double().reshape(-1)
-        names.append(k)
-        rows.append([float(d.sum()), float(d.abs().sum()), float(d[0]), float(d[-1]), float(d.numel())])
+    threads = torch.get_num_threads()
+    torch.set_num_threads(PIN_THREADS)
+    try:
+        for k, v in state_dict.items():
+            if not v.dtype.is_floating_point:
+                continue
+            d = v.detach().double().reshape(-1)
+            names.append(k)
+            rows.append([float(d.sum()), float(d.abs().sum()), float(d[0]), float(d[-1]), float(d.numel())])
+    finally:
+        torch.set_num_threads(threads)
     return names, np.array(rows, dtype=np.float64)
 
 
@@ -61,7 +71,19 @@ def test_init_weights_same_seed_equals_reference(golden, tag, path):
         want_names = [str(x) for x in g["%s.%s.names" % (tag, part)]]
         assert names == want_names, (tag, part)                     # same keys, same registration order
         want = g["%s.%s.pins" % (tag, part)].numpy()
-        bad = [n for n, a, b in zip(names, rows, want) if not np.array_equal(a, b)]
+        sd = mod.state_dict()
+        bad = []
+        for n, a, b in zip(names, rows, want):
+            if n.endswith("positional_encoder.inv_timescales"):
+                # not drawn from the seed but exp() of a constant: the host's math library rounds it (faithful to about an
+                # ulp, not bit-identical across CPU vendors) -- the reference's formula on this host bit for bit, and the
+                # captured checksums to a few ulps
+                nts = sd[n].numel()
+                assert torch.equal(sd[n], torch.exp(torch.arange(nts).float() * -(math.log(1.0e4) / nts))), n
+                if not np.allclose(a, b, rtol=4 * 2.0 ** -24, atol=0):
+                    bad.append(n)
+            elif not np.array_equal(a, b):
+                bad.append(n)
         assert not bad, (tag, part, bad[:5])                        # bit-identical tensors (checksums in float64)
 
 
