@@ -472,15 +472,7 @@ __global__ __launch_bounds__(512, 1) void lvt_attn_fwd_flash_kernel(const FaArgs
 // encoder layer's w_q (tests/test_gpu_vt.py, G12).  The pass therefore also accumulates C_i = sum_j p_ij K_j at fp16 precision
 // (one MFMA per 16 dims on the hi plane of the K^T fragments that dQ loads anyway) and the realised row sum eps_i = sum_j g_ij,
 // returns dQ_i - eps_i C_i / temper, and hands kernel B delta + eps (B then forms g as the two-pass form did).
-#ifndef FA_EARLY_LOADS
-#define FA_EARLY_LOADS 1                    // kernel A (0: its prologue requests q, dO, o one after the other, the round-5 order)
-#endif
-#ifndef FB_EARLY_LOADS
-#define FB_EARLY_LOADS 0                    // kernel B: measured 161.4 / 158.5 -> 164.5 / 160.7 us with it (A: 198.8 / 196.5 -> 196.9 / 192.9)
-#endif
-#ifndef LVT_FA_A_CORR
-#define LVT_FA_A_CORR 1                   // (timing builds: 0 = one pass without the C_i accumulation -- fails G12's w_q bound)
-#endif
+// (The same prologue reordering in kernel B measured slower, 161.4 / 158.5 -> 164.5 / 160.7 us, and was not kept: DESIGN 3.5.)
 template <int BT, int BH, int BW, int MASKED, int NCH, int ONEP>
 __device__ __forceinline__ float fa_bwd_a_body(const FaArgs &A, FaSmemA<BT + Geo16<BH, BW>::HP + 4> &sm, int bh_, int qhalf) {
     using GE = Geo16<BH, BW>;
@@ -508,7 +500,6 @@ __device__ __forceinline__ float fa_bwd_a_body(const FaArgs &A, FaSmemA<BT + Geo
     load_item(0, g0);
     f16x8 qb[4][2], dob[4][2];
     float qinv, doinv;
-#if FA_EARLY_LOADS
     // q, dO and (one pass) the forward's output row of this lane's query are requested TOGETHER, then split: one round of
     // global-load latency instead of three dependent ones (q -> split, dO -> split, and after the first barrier o / dO again for
     // delta = dO . O, which reads exactly the 32 columns of the dO fragments)
@@ -529,10 +520,6 @@ __device__ __forceinline__ float fa_bwd_a_body(const FaArgs &A, FaSmemA<BT + Geo
         }
         delta_early = fa_kg_sum(a0 + a1);
     }
-#else
-    fa_load_bfrags(A.q + (row0 + i) * A.ld + h * AT_D, kg, qb, qinv);
-    fa_load_bfrags(A.d_o + (row0 + i) * A.ld + h * AT_D, kg, dob, doinv);
-#endif
     const long long si = ((long long)b * A.H + h) * AT_S + i;
     const float m_i = A.m[si], linv = A.l[si];
     const int wi = i % BW, hi = (i / BW) % BH, ti = i / (BW * BH);
@@ -554,28 +541,11 @@ __device__ __forceinline__ float fa_bwd_a_body(const FaArgs &A, FaSmemA<BT + Geo
     float sgf = 0.f, kmr = 0.f, dl = 0.f;                             // pass 2: scale of g from its bound, 1 / kmax (applied one
                                                                       // after the other: their product can leave the float range), delta / l
     int ebG = FA_EMIN;                                                // ONEP: the running exponent of max |g 2^(e_K - 14)| of this query row
-#if FA_EARLY_LOADS
     if constexpr (ONEP) { delta = delta_early; dl = delta * linv; }
-#else
-    if constexpr (ONEP) {
-        // delta_i = dO_i . O_i: the lane's 32 columns (those of its B fragments), then the four lanes of the column
-        const float *orow = A.o + (row0 + i) * A.ld + h * AT_D + 8 * kg, *drow = A.d_o + (row0 + i) * A.ld + h * AT_D + 8 * kg;
-        float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-        for (int s_ = 0; s_ < 4; ++s_) {
-            const float4 o0 = *reinterpret_cast<const float4 *>(orow + 32 * s_), o1 = *reinterpret_cast<const float4 *>(orow + 32 * s_ + 4);
-            const float4 d0 = *reinterpret_cast<const float4 *>(drow + 32 * s_), d1 = *reinterpret_cast<const float4 *>(drow + 32 * s_ + 4);
-            a0 = fmaf(o0.x, d0.x, a0); a0 = fmaf(o0.y, d0.y, a0); a0 = fmaf(o0.z, d0.z, a0); a0 = fmaf(o0.w, d0.w, a0);
-            a1 = fmaf(o1.x, d1.x, a1); a1 = fmaf(o1.y, d1.y, a1); a1 = fmaf(o1.z, d1.z, a1); a1 = fmaf(o1.w, d1.w, a1);
-        }
-        delta = fa_kg_sum(a0 + a1);
-        dl = delta * linv;
-    }
-#endif
     f32x4v qacc[AT_D / 16];
 #pragma unroll
     for (int d = 0; d < AT_D / 16; ++d) qacc[d] = f32x4v{0.f, 0.f, 0.f, 0.f};
-    constexpr bool CORR = ONEP && LVT_FA_A_CORR;
+    constexpr bool CORR = ONEP;
     f32x4v cacc[CORR ? AT_D / 16 : 1];                               // ONEP: C_i = sum_j p_ij K_j under the scale 2^(268 - ebC)
 #pragma unroll
     for (int d = 0; d < (CORR ? AT_D / 16 : 1); ++d) cacc[d] = f32x4v{0.f, 0.f, 0.f, 0.f};
@@ -876,31 +846,18 @@ __device__ __forceinline__ float fa_bwd_b_body(const FaArgs &A, FaSmemB &sm, int
     auto load_item = [&](int t, G4 &gg) {
         fa_load(gg, qbase + (long long)(32 * (C0 + t)) * A.ld, dobase + (long long)(32 * (C0 + t)) * A.ld, A.ld, tid);
     };
-    float4 kraw[8];
     {                                   // the workgroup's 128 V rows -> LDS, resident
         const float *rows = A.v + (row0 + khalf * 128) * A.ld + h * AT_D;
         G4 a, bq;
         fa_load(a, rows, rows + 32 * A.ld, A.ld, tid);
         fa_load(bq, rows + 64 * A.ld, rows + 96 * A.ld, A.ld, tid);
-#if FB_EARLY_LOADS
-        // the first Q | dO item and the wave's K rows are requested BEFORE the V rows are split and stored: one round of global-load
-        // latency per workgroup instead of two (four workgroups per CU and launch, nothing beside a prologue to hide it)
-        load_item(0, g0);
-        fa_bfrags_request(A.k + (row0 + j) * A.ld + h * AT_D, kg, kraw);
-#endif
-#ifdef FB_X_NOVSTAGE
-        if (A.H < 0)
-#endif
-        { fa_park(a, sm.vres[0], sm.vinv[0], tid); fa_park(bq, sm.vres[1], sm.vinv[1], tid); }
+        fa_park(a, sm.vres[0], sm.vinv[0], tid);
+        fa_park(bq, sm.vres[1], sm.vinv[1], tid);
     }
     f16x8 kb[4][2];
     float kinv;
-#if FB_EARLY_LOADS
-    fa_bfrags_split(kraw, kb, kinv);
-#else
     load_item(0, g0);
     fa_load_bfrags(A.k + (row0 + j) * A.ld + h * AT_D, kg, kb, kinv);
-#endif
     // bounds from kernel A (both query halves): exponent of the dO rows, bound of g 2^(e_q - 14)
     const float *sc = A.scal + (long long)bh_ * 4;
     const float domax = fmaxf(sc[0], sc[2]), umax = fmaxf(sc[1], sc[3]);
@@ -958,12 +915,6 @@ __device__ __forceinline__ float fa_bwd_b_body(const FaArgs &A, FaSmemB &sm, int
             for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
                 for (int pl = 0; pl < 2; ++pl) aq[bf][qt][pl] = fa_rowfrag(cur, pl, 16 * qt + c16, s_, kg);
-#ifdef FB_X_NOFRAG1
-#pragma unroll
-            for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl) aq[bf][qt][pl] = kb[s_ & 3][pl];
-#endif
         };
         auto load_p = [&](int s_) {
 #pragma unroll
@@ -972,23 +923,11 @@ __device__ __forceinline__ float fa_bwd_b_body(const FaArgs &A, FaSmemB &sm, int
             for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
                 for (int pl = 0; pl < 2; ++pl) ad[qt][pl] = fa_rowfrag(cur, pl, 32 + 16 * qt + c16, s_, kg);
-#ifdef FB_X_NOFRAG1
-            vb[0] = kb[s_ & 3][1]; vb[1] = kb[s_ & 3][0];
-#pragma unroll
-            for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl) ad[qt][pl] = kb[(s_ + 1) & 3][pl];
-#endif
         };
         load_s(0, 0);
         static_for<4>([&](auto sc_) {
             constexpr int s = decltype(sc_)::value, bf = s & 1;
             load_p(s);
-#ifdef FB_X_NOMFMA1
-#pragma unroll
-            for (int qt = 0; qt < 2; ++qt) { st[qt] += __builtin_bit_cast(f32x4v, aq[bf][qt][1]) + __builtin_bit_cast(f32x4v, aq[bf][qt][0]); dp[qt] += __builtin_bit_cast(f32x4v, ad[qt][0]) + __builtin_bit_cast(f32x4v, ad[qt][1]) + __builtin_bit_cast(f32x4v, vb[0]) + __builtin_bit_cast(f32x4v, vb[1]); }
-            if constexpr (s < 3) load_s(s + 1, bf ^ 1);
-#else
 #pragma unroll
             for (int qt = 0; qt < 2; ++qt) st[qt] = fa_mfma(aq[bf][qt][1], kb[s][0], st[qt]);
 #pragma unroll
@@ -1002,15 +941,12 @@ __device__ __forceinline__ float fa_bwd_b_body(const FaArgs &A, FaSmemB &sm, int
             for (int qt = 0; qt < 2; ++qt) dp[qt] = fa_mfma(ad[qt][0], vb[1], dp[qt]);
 #pragma unroll
             for (int qt = 0; qt < 2; ++qt) dp[qt] = fa_mfma(ad[qt][0], vb[0], dp[qt]);
-#endif
-#ifndef FB_X_NOPARK
             if constexpr (PARK) {
                 if constexpr (s == 0) eb0 = fa_row_scale(g0.v[0], g0.v[1]);
                 if constexpr (s == 1) fa_row_store(g0.v[0], g0.v[1], eb0, nslot, ninv, tid >> 4, tid & 15);
                 if constexpr (s == 2) eb1 = fa_row_scale(g0.v[2], g0.v[3]);
                 if constexpr (s == 3) fa_row_store(g0.v[2], g0.v[3], eb1, nslot, ninv, 32 + (tid >> 4), tid & 15);
             }
-#endif
             // pin the order: [dO / V reads] [S MFMAs + staging arithmetic] [next Q reads] [dP MFMAs + staging arithmetic]
             __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
 #pragma unroll
@@ -1029,10 +965,6 @@ __device__ __forceinline__ float fa_bwd_b_body(const FaArgs &A, FaSmemB &sm, int
         if constexpr (t + 2 < NIT) load_item(t + 2, g0);
         // ---- element-wise: per tile the products of the row / column factors, per element five operations + the mask ----
         float pw[8], u[8];
-#ifdef FB_X_NOEW
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { pw[e] = st[e >> 2][e & 3]; u[e] = dp[e >> 2][e & 3]; }
-#else
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) {
             const int T = 2 * c + qt;                                 // 16-query tile of the (sample, head)
@@ -1052,7 +984,6 @@ __device__ __forceinline__ float fa_bwd_b_body(const FaArgs &A, FaSmemB &sm, int
                 u[4 * qt + r] = (ex * fmaf(dp[qt][r], dvq[r], -dq_[r])) * zrun;     // (zrun last: |g 2^(e_i - 14)| <= the bound it comes from)
             }
         }
-#endif
         f16x8 pbh, pbl, ubh, ubl;
         fa_split8(pw, pbh, pbl);
         fa_split8(u, ubh, ubl);
@@ -1062,23 +993,12 @@ __device__ __forceinline__ float fa_bwd_b_body(const FaArgs &A, FaSmemB &sm, int
         auto load_o = [&](int d_, int bf) {
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl) ao[bf][pl] = fa_trfrag(cur, pl, 32, d_, c16, kg);
-#ifdef FB_X_NOFRAG3
-            ao[bf][0] = kb[d_ & 3][0]; ao[bf][1] = kb[d_ & 3][1];
-#endif
         };
         load_o(0, 0);
         static_for<AT_D / 16>([&](auto dc) {
             constexpr int d = decltype(dc)::value, bf = d & 1;
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl) aqt[pl] = fa_trfrag(cur, pl, 0, d, c16, kg);
-#ifdef FB_X_NOFRAG3
-            aqt[0] = kb[(d + 1) & 3][0]; aqt[1] = kb[(d + 1) & 3][1];
-#endif
-#ifdef FB_X_NOMFMA3
-            accv[d] += __builtin_bit_cast(f32x4v, ao[bf][1]) + __builtin_bit_cast(f32x4v, ao[bf][0]) + __builtin_bit_cast(f32x4v, pbh) + __builtin_bit_cast(f32x4v, pbl);
-            if constexpr (d + 1 < AT_D / 16) load_o(d + 1, bf ^ 1);
-            acck[d] += __builtin_bit_cast(f32x4v, aqt[1]) + __builtin_bit_cast(f32x4v, aqt[0]) + __builtin_bit_cast(f32x4v, ubh) + __builtin_bit_cast(f32x4v, ubl);
-#else
             accv[d] = fa_mfma(ao[bf][1], pbh, accv[d]);
             accv[d] = fa_mfma(ao[bf][0], pbl, accv[d]);
             accv[d] = fa_mfma(ao[bf][0], pbh, accv[d]);
@@ -1086,7 +1006,6 @@ __device__ __forceinline__ float fa_bwd_b_body(const FaArgs &A, FaSmemB &sm, int
             acck[d] = fa_mfma(aqt[1], ubh, acck[d]);
             acck[d] = fa_mfma(aqt[0], ubl, acck[d]);
             acck[d] = fa_mfma(aqt[0], ubh, acck[d]);
-#endif
             __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
             if constexpr (d + 1 < AT_D / 16) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
@@ -1103,10 +1022,8 @@ __device__ __forceinline__ float fa_bwd_b_body(const FaArgs &A, FaSmemB &sm, int
 #pragma unroll
         for (int d = 0; d < AT_D / 16; ++d) {
             const f32x4v ov = accv[d] * fvs, ok = acck[d] * fks;
-#ifdef FB_X_NOSTORE
-            if (A.H < 0)
-#endif
-            { *reinterpret_cast<f32x4v *>(vrow + 16 * d) = ov; *reinterpret_cast<f32x4v *>(krow + 16 * d) = ok; }
+            *reinterpret_cast<f32x4v *>(vrow + 16 * d) = ov;
+            *reinterpret_cast<f32x4v *>(krow + 16 * d) = ok;
 #pragma unroll
             for (int e = 0; e < 4; ++e) am = fmaxf(am, fmaxf(fabsf(ov[e]), fabsf(ok[e])));
         }
@@ -1211,10 +1128,9 @@ extern "C" int lvt_attn_bwd_flash(const float *q, const float *k, const float *v
     A.q = q; A.k = k; A.v = v; A.d_o = d_o; A.ld = ld; A.H = H; A.inv_temper = 1.f / temper; A.c1 = FA_LOG2E / temper; A.fill2 = fill * FA_LOG2E;
     A.dt = dt; A.dh = dh; A.dw = dw; A.m = const_cast<float *>(stats); A.l = const_cast<float *>(stats) + (size_t)B * H * S;
     A.dq = dq; A.dk = dk; A.dv = dv;
-    // o (the forward's output, row stride ld) selects the one-pass form of kernel A; NULL (or LVT_FA_TWOPASS): delta from a first pass over the keys
-    static const int twopass = getenv("LVT_FA_TWOPASS") ? 1 : 0;
+    // o (the forward's output, row stride ld) selects the one-pass form of kernel A; NULL: delta from a first pass over the keys
     LVT_REQUIRE(!o || lvt_aligned16(o), "attn_bwd_flash: o must be 16-byte aligned");
-    const bool onep = o && !twopass;
+    const bool onep = o != nullptr;
     A.o = const_cast<float *>(o);
     A.delta = (float *)workspace;
     A.scal = A.delta + (size_t)B * H * S;

@@ -28,13 +28,6 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 #define WG_CQ 256
 #define WG_QP (WG_CQ + 32)               // slab pixel pitch (bf16): 576 B = 16 dwords mod 64
 #define WG_QPL (16 * WG_QP)
-#ifndef LVT_WG_ANTIPHASE_MODES
-#define LVT_WG_ANTIPHASE_MODES 2         // bit MODE: the stride-2 kernel (24 MFMAs per staged row) gains, the 3x3 one (54) does not
-#endif
-#ifndef LVT_WG_S2_PAIR
-#define LVT_WG_S2_PAIR 1                 // stride-2 kernel in f16x2: two parity classes per workgroup (0: one, the round-4 form)
-#endif
-#define LVT_WG_ANTIPHASE(mode) (((LVT_WG_ANTIPHASE_MODES) >> (mode)) & 1)
 
 struct WgParams {
     const float *P, *Q;
@@ -122,7 +115,7 @@ __device__ __forceinline__ bf16x8 wg_frag(const unsigned short *p, int pitch4) {
 
 template <int MODE, int MATH>
 __global__ __launch_bounds__(WG_THREADS) void lvt_conv_wgrad_frames_kernel(const WgParams p) {
-    constexpr int NCLS = (MODE == 1 && MATH == 2 && LVT_WG_S2_PAIR) ? 2 : 1;         // parity classes (patch images) per workgroup
+    constexpr int NCLS = (MODE == 1 && MATH == 2) ? 2 : 1;         // parity classes (patch images) per workgroup (one: the round-4 form)
     constexpr int NTAPS = MODE == 0 ? 9 : 4 * NCLS;
     constexpr int NP = MATH == 2 ? 2 : 3;
     __shared__ __attribute__((aligned(16))) unsigned short lds[NCLS * NP * WG_PPL + 2 * NP * WG_QPL];
@@ -261,7 +254,9 @@ __global__ __launch_bounds__(WG_THREADS) void lvt_conv_wgrad_frames_kernel(const
     // split / store the next slab row and then both queue on the matrix pipe.  Waves 4..7 ("early") therefore store row r + 1
     // BEFORE their MFMAs of row r (their fetch runs two rows ahead), waves 0..3 after them: on every SIMD one wave converts
     // while the other multiplies.  (Both orders sit between the same two barriers; each thread stores its own part of a row.)
-    const bool early = LVT_WG_ANTIPHASE(MODE) && NCLS == 1 && ((wave >> 2) & 1);     // (two images: 24 MFMAs per row in f16x2, in phase is 2 % faster)
+    // (It pays in the stride-2 kernel, 24 MFMAs per staged row, not in the 3x3 one, 54; with two images, 24 MFMAs per row in f16x2,
+    // in phase is 2 % faster.)
+    const bool early = MODE == 1 && NCLS == 1 && ((wave >> 2) & 1);
     const int r_end = f1 * 16;
     auto slab_fetch_row = [&](int r) { if (r < r_end) slab_fetch(r >> 4, r & 15); };
     if (f0 < f1) {
@@ -402,22 +397,20 @@ __global__ void lvt_wgrad_bias_reduce_kernel(const float *__restrict__ colsum_pa
 // ---- host side (called from lvt_conv3d_bwd_weight in gemm_engine.hip) -----------------------------------------------
 // 0: not served; 1: 3x3, patch = x / slab = dy; 2: 3x3 swapped; 3: 4x4 stride 2, patch = x (32x32 frames) / slab = dy (256 ch)
 static int wg_role(const lvt_conv_geom *g, int flags = 0) {
-    static const int off = getenv("LVT_NO_FRAME_WGRAD") ? 1 : 0;
-    static const int off2 = getenv("LVT_NO_FRAME_WGRAD_S2") ? 1 : 0;
-    if (off || (flags & LVT_MATH_F32)) return 0;                // (bf16x3 and f16x2 are both served)
+    if (flags & LVT_MATH_F32) return 0;                // (bf16x3 and f16x2 are both served)
     if (g->Kt != 1 || g->pt != 0 || g->Ti != 1 || g->To != 1 || g->st != 1 || g->Ho != 16 || g->Wo != 16) return 0;
     if (g->Kh == 3 && g->Kw == 3 && g->sh == 1 && g->sw == 1 && g->ph == 1 && g->pw == 1 && g->Hi == 16 && g->Wi == 16) {
         if (g->Co == WG_CQ && g->Ci % 32 == 0) return 1;
         if (g->Ci == WG_CQ && g->Co % 32 == 0) return 2;
     }
-    if (!off2 && g->Kh == 4 && g->Kw == 4 && g->sh == 2 && g->sw == 2 && g->ph == 1 && g->pw == 1 && g->Hi == 32 && g->Wi == 32 &&
+    if (g->Kh == 4 && g->Kw == 4 && g->sh == 2 && g->sw == 2 && g->ph == 1 && g->pw == 1 && g->Hi == 32 && g->Wi == 32 &&
         g->Co == WG_CQ && g->Ci % 32 == 0)
         return 3;
     return 0;
 }
 static int wg_splits(const lvt_conv_geom *g, int role, bool f16) {
     // (role 3: four parity classes per chunk, two per workgroup in f16x2)
-    const int jobs = role == 3 ? (f16 && LVT_WG_S2_PAIR ? 2 : 4) * (g->Ci / 32) : (role == 1 ? g->Ci : g->Co) / 32;
+    const int jobs = role == 3 ? (f16 ? 2 : 4) * (g->Ci / 32) : (role == 1 ? g->Ci : g->Co) / 32;
     int s = 256 / jobs;                            // one workgroup per CU (118 KB of LDS each): a single full wave
     if (s > g->N) s = g->N;
     return s < 1 ? 1 : s;
@@ -440,7 +433,7 @@ int lvt_wgrad_frames_launch(const lvt_conv_geom *g, const float *x, const float 
     p.p_amax = role == 2 ? dy_amax : x_amax; p.q_amax = role == 2 ? x_amax : dy_amax;
     p.Cp = role == 2 ? g->Co : g->Ci; p.N = g->N; p.nchunks = p.Cp / 32;
     const int splits = wg_splits(g, role, f16);
-    const int ncls = role == 3 ? (f16 && LVT_WG_S2_PAIR ? 2 : 4) : 1;         // class jobs per chunk
+    const int ncls = role == 3 ? (f16 ? 2 : 4) : 1;         // class jobs per chunk
     p.frames_per_split = (g->N + splits - 1) / splits;
     p.partial = (float *)workspace; p.partial_stride = (long long)g->Kh * g->Kw * g->Ci * g->Co;
     // dy is the patch operand in role 2, the slab (256 = Co channels) otherwise; x (db_of_x: role 3 only) is the patch operand there

@@ -365,9 +365,7 @@ __global__ void lvt_layernorm_fwd_kernel(const float *__restrict__ x, long long 
     }
     if (y_amax) lvt_block_amax_commit(am, y_amax, amax_scratch);
 }
-#ifndef LN_FWD_MAX_BLOCKS
 #define LN_FWD_MAX_BLOCKS 16384
-#endif
 extern "C" int lvt_layernorm_fwd(const float *x, long long rows, int d, float eps, const float *w, const float *b,
                                  float *y, float *mean, float *rstd, float *y_amax, const float *w_amax, const float *b_amax,
                                  void *stream) {
@@ -393,12 +391,8 @@ extern "C" int lvt_layernorm_fwd_p2(const float *x, long long rows, int d, float
 // dx = rstd * (dy*w - mean(dy*w) - xhat * mean(dy*w*xhat)) (+ add);  partial dw/db per workgroup
 // 512 workgroups (2 per CU): measured at 16384 x 512, bwd+add 28.0 us against 32.7 us at 1024 and 33 us at 256; more rows in flight
 // per wave (LN_BWD_ROWS 2 / 4) measured 28.6 / 39.1 us (tools/profile/ln_time.py)
-#ifndef LN_BWD_BLOCKS
 #define LN_BWD_BLOCKS 512
-#endif
-#ifndef LN_BWD_ROWS
 #define LN_BWD_ROWS 1
-#endif
 __global__ __launch_bounds__(256) void lvt_layernorm_bwd_kernel(
     const float *__restrict__ dy, const float *__restrict__ x, const float *__restrict__ mean,
     const float *__restrict__ rstd, const float *__restrict__ w, long long rows, int d, const float *__restrict__ add,

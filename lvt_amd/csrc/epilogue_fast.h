@@ -75,10 +75,7 @@ __device__ __forceinline__ float lvt_epi_fast_wave(const LvtEpi &e, lvt_f32x16 (
     float am = 0.f;
     // residual / mask rows of BOTH 32-row rounds are requested up front: requested per round (round 6, first form) a cold operand --
     // the saved hidden activation that masks the FFN data gradient comes from HBM -- exposed its latency once per round (the
-    // 16384 x 512 x 512 product with a mask 51 us against 37 without).  LVT_EPI_LATE_LOADS=1: the per-round form (A/B switch).
-#ifndef LVT_EPI_LATE_LOADS
-#define LVT_EPI_LATE_LOADS 0
-#endif
+    // 16384 x 512 x 512 product with a mask 51 us against 37 without).
     long long orow_all[TM][8];
     float4 rv_all[TM][8], mv_all[TM][8];
 #pragma unroll
@@ -102,10 +99,8 @@ __device__ __forceinline__ float lvt_epi_fast_wave(const LvtEpi &e, lvt_f32x16 (
                 mv_all[i][u] = (colok && row0 + 4 * u < e.M) ? *reinterpret_cast<const float4 *>(mp + orow_all[i][u] * e.ldm) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     };
-    if (!LVT_EPI_LATE_LOADS) {
 #pragma unroll
-        for (int i = 0; i < TM; ++i) request(i);
-    }
+    for (int i = 0; i < TM; ++i) request(i);
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -113,7 +108,6 @@ __device__ __forceinline__ float lvt_epi_fast_wave(const LvtEpi &e, lvt_f32x16 (
 #pragma unroll
             for (int r = 0; r < 16; ++r) wave_tile[((r & 3) + 8 * (r >> 2) + 4 * half) * SW + 32 * j + l31] = acc[i][j][r];
         const int row0 = m_w + i * 32 + r0;                                  // rows row0 + 4 u, u = 0 .. 7
-        if (LVT_EPI_LATE_LOADS) request(i);
         const long long (&orow)[8] = orow_all[i];
         const float4 (&rv)[8] = rv_all[i];
         const float4 (&mv)[8] = mv_all[i];

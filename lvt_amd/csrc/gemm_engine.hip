@@ -27,13 +27,7 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-#ifndef LVT_BK
-#define LVT_BK 32
-#endif
-#define BK LVT_BK
-#ifndef LVT_MINWAVES
-#define LVT_MINWAVES 1
-#endif
+#define BK 32
 #define NTHREADS 256
 
 enum { A_KPLAIN = 0, A_MPLAIN = 1, A_CONV_K = 2, A_CONVT_K = 3, A_CONV_M = 4, A_ONEHOT_M = 5, A_PATCH = 6, A_PATCHT = 7 };
@@ -194,12 +188,6 @@ template <int ROWS, int LEAN = 0> __device__ __forceinline__ void store_split2_k
     *reinterpret_cast<uint2 *>(d) = ph;
     *reinterpret_cast<uint2 *>(d + HPlane<ROWS>::SIZE) = pl;
 }
-// (timing experiments LVT_WX_ARAW / LVT_WX_BRAW: the operand arrives as ready fp16 planes -- same bytes, no arithmetic)
-template <int ROWS> __device__ __forceinline__ void store_raw2_k(unsigned short *lds, int row, int k4, const float4 v) {
-    unsigned short *d = lds + hrow<ROWS>(row) + k4;
-    *reinterpret_cast<uint2 *>(d) = make_uint2(__float_as_uint(v.x), __float_as_uint(v.y));
-    *reinterpret_cast<uint2 *>(d + HPlane<ROWS>::SIZE) = make_uint2(__float_as_uint(v.z), __float_as_uint(v.w));
-}
 template <int ROWS, int LEAN = 0> __device__ __forceinline__ void store_split2_m(unsigned short *lds, int row4, int k, const float4 v, float s) {
     uint2 p[2];
     if (LEAN) split2_lean(v, s, p[0], p[1]);
@@ -247,7 +235,7 @@ template <int MODE, int BM, int MATH> struct ALoader;
 // ---- k-contiguous family: rows r0 + 32*i (i < BM/32), k quad kq = tid & 7 ------------------------
 #define QPR (BK / 4)                 // float4 quads per tile row
 #define RPP (NTHREADS / QPR)         // tile rows covered per pass
-#define KPAD (BK == 32 ? 1 : 2)      // row pad that keeps the transposing stores conflict-free
+#define KPAD 1                       // row pad that keeps the transposing stores conflict-free
 template <int MODE, int BM> struct AKLoaderBase {
     static constexpr int ITERS = BM / RPP;
     static constexpr int LD = BM + KPAD;
@@ -1006,7 +994,7 @@ __device__ __forceinline__ void lvt_epilogue_vec(const KParams &p, f32x16 (&acc)
 // MATH == 2: f16x2 split -- two fp16 planes per operand after an exact power-of-two scale from the operand's max |.|
 //            (split2 above), three v_mfma_f32_32x32x16_f16 per block into two accumulators.  Half the MFMAs of MATH == 1.
 template <int AMODE, int BMODE, int BM, int BN, int WM, int WN, int MATH>
-__global__ __launch_bounds__(NTHREADS, (MATH == 2 ? 2 : LVT_MINWAVES)) void lvt_gemm_kernel(const KParams p) {
+__global__ __launch_bounds__(NTHREADS, (MATH == 2 ? 2 : 1)) void lvt_gemm_kernel(const KParams p) {
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
     using AL = ALoader<AMODE, BM, MATH>;
     using BL = BLoader<BMODE, BN, MATH>;
@@ -1178,7 +1166,6 @@ __global__ __launch_bounds__(NTHREADS, (MATH == 2 ? 2 : LVT_MINWAVES)) void lvt_
     if constexpr (COLSUM_A) {
         if (al.sum_on) al.write_colsum(lds, p.colsum_partial + ((long long)split * gridDim.y + z) * p.M, m0, p.M, tid);
     }
-#ifndef LVT_NO_FAST_EPILOGUE
     if constexpr (AMODE != A_CONVT_K && TM == 2 && TN == 2 && LDS_FLOATS >= TURN_FLOATS + 16) {
         if (p.vec_epi && !(p.flags & (LVT_EPI_PLANES | LVT_EPI_ACCUM | LVT_EPI_TANH))) {
             // every form whose tile rows ARE the rows of C: epilogue_fast.h (same arithmetic, see there)
@@ -1200,7 +1187,6 @@ __global__ __launch_bounds__(NTHREADS, (MATH == 2 ? 2 : LVT_MINWAVES)) void lvt_
             return;
         }
     }
-#endif
     if (p.vec_epi) lvt_epilogue_vec<AMODE, BM, BN, WM, WN>(p, acc, lds, m0, n0, wm, wn, lane, cls, coff, z, split);
     else lvt_epilogue<AMODE, BM, BN, WM, WN>(p, acc, m0, n0, wm, wn, l31, half, cls, coff, z, split);
 }
@@ -1246,11 +1232,8 @@ __global__ __launch_bounds__(PT_THREADS) void lvt_conv_patch_kernel(const KParam
     constexpr int PSB = HPlane<BN>::SIZE;
     // f16x2 (two planes): TWO patch images -- the patch of chunk c + 1 is fetched during the second-to-last tap step of chunk c
     // and split + stored into the other image right behind the last tap step's MFMAs, instead of between two barriers
-    // of its own with the matrix pipe idle (bf16x3: three planes, one image fits).  -DLVT_PX_ONE_PATCH=1: the round-4 form.
-#ifndef LVT_PX_ONE_PATCH
-#define LVT_PX_ONE_PATCH 0
-#endif
-    constexpr bool DBLA = MATH == 2 && !LVT_PX_ONE_PATCH;
+    // of its own with the matrix pipe idle (bf16x3: three planes, one image fits).  The round-4 form had one image: DESIGN 3.2.
+    constexpr bool DBLA = MATH == 2;
     constexpr int A_IMG = NP * PT_PLANE;                                      // one patch image (bf16 / fp16 elements)
     constexpr int A_BYTES = A_IMG * 2 * (DBLA ? 2 : 1), B_BYTES = NP * PSB * 2;
     constexpr int STAGE_FLOATS = (A_BYTES + 2 * B_BYTES) / 4 + 8;
@@ -1464,21 +1447,15 @@ __global__ __launch_bounds__(PT_THREADS) void lvt_conv_patch_kernel(const KParam
             }
         }
         // the other weight buffer was last read in the previous step, which every wave has left (barrier below)
-#ifndef LVT_PX_NOBSPLIT      // (timing experiment: the weight tile is split + stored for step 0 only)
         if (!BIMG && has_next && bact) b_store(Bh0 + ((step + 1) & 1) * (NP * PSB));
-#endif
         if (!DBLA && new_chunk) {
             __syncthreads();              // every wave is done with the old patch
             patch_store(Ah);
         }
         if (BIMG && has_next) b_landed(Bh0 + ((step + 1) & 1) * (NP * PSB));
-#ifdef LVT_PX_HALFBARRIERS   // (timing experiment, wrong results: a barrier every second step)
-        if ((step & 1) || new_chunk)
-#endif
         __syncthreads();
     }
     if constexpr (MATH == 2) lvt_f16x2_finish<TM, TN>(acc, acx, unscale);
-#ifndef LVT_NO_FAST_EPILOGUE
     if (p.vec_epi && p.splits <= 1 && !(p.flags & (LVT_EPI_PLANES | LVT_EPI_ACCUM | LVT_EPI_TANH))) {
         // epilogue_fast.h with the pixel permutation of the frame as its row map
         const unsigned seen = lvt_amax_peek(p.c_amax);
@@ -1492,7 +1469,6 @@ __global__ __launch_bounds__(PT_THREADS) void lvt_conv_patch_kernel(const KParam
         if (p.c_amax) lvt_block_amax_commit_seen(am_w, p.c_amax, lds + TURN_FLOATS, seen);
         return;
     }
-#endif
     if (MODE != 1) lvt_epilogue_vec<A_PATCH, BM, BN, WM, WN>(p, acc, lds, m0, n0, wm, wn, lane, 0, 0, 0, 0);
     else lvt_epilogue_vec<A_PATCHT, BM, BN, WM, WN>(p, acc, lds, m0, n0, wm, wn, lane, phase, 0, 0, 0);
 }
@@ -1608,21 +1584,13 @@ __global__ __launch_bounds__(WIDE_THREADS, 2) void lvt_gemm_wide_kernel(const KP
         unsigned short *Ah = buf, *Bh = buf + 2 * PSA;
         if (!TA) {
 #pragma unroll
-#ifdef LVT_WX_ARAW
-            for (int i = 0; i < 4; ++i) store_raw2_k<BM>(Ah, r0 + 64 * i, kq * 4, av[i]);
-#else
             for (int i = 0; i < 4; ++i) store_split2_k<BM>(Ah, r0 + 64 * i, kq * 4, av[i], sa);
-#endif
         } else {
             store_split2_block<BM>(Ah, mq * 4, kk0 * 4, av, sa);
         }
         if (!TB) {
 #pragma unroll
-#ifdef LVT_WX_BRAW
-            for (int i = 0; i < 2; ++i) store_raw2_k<BN>(Bh, r0 + 64 * i, kq * 4, bv[i]);
-#else
             for (int i = 0; i < 2; ++i) store_split2_k<BN>(Bh, r0 + 64 * i, kq * 4, bv[i], sb);
-#endif
         } else if (bact) {
             store_split2_block<BN>(Bh, bnq * 4, bkk0 * 4, bv, sb);
         }
@@ -1658,15 +1626,6 @@ __global__ __launch_bounds__(WIDE_THREADS, 2) void lvt_gemm_wide_kernel(const KP
 #pragma unroll
                 for (int j = 0; j < TN; ++j) b[q][j] = *reinterpret_cast<const f16x8 *>(cur + fb[j] + q * PSB + ks);
             }
-#ifdef LVT_WX_NOMFMA        // (timing experiments, tools/profile/build_variant.sh: what the main loop costs without one of its parts)
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    acc[i][j][0] += (float)a[0][i][0] + (float)b[0][j][0] + (float)a[1][i][1] + (float)b[1][j][1];
-                    acx[i][j][0] += (float)a[0][i][7] + (float)b[0][j][7];
-                }
-#else
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1682,14 +1641,9 @@ __global__ __launch_bounds__(WIDE_THREADS, 2) void lvt_gemm_wide_kernel(const KP
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
                     acx[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][i], b[0][j], acx[i][j], 0, 0, 0);
-#endif
             if (ks == 0) {
-#ifndef LVT_WX_NOSPLIT
                 if constexpr (decltype(do_store)::value) store(nxt);
-#endif
-#ifndef LVT_WX_NOFETCH
                 if constexpr (decltype(do_fetch)::value) fetch();
-#endif
             }
         }
     };
@@ -1706,9 +1660,7 @@ __global__ __launch_bounds__(WIDE_THREADS, 2) void lvt_gemm_wide_kernel(const KP
     int kt = 0;
     for (; kt + 2 < ntiles; ++kt) {
         tile(S0 + (kt & 1) * STAGE, S0 + ((kt + 1) & 1) * STAGE, yes_t(), yes_t());
-#ifndef LVT_WX_NOBARRIER    // (timing experiment, wrong results)
         __syncthreads();
-#endif
     }
     if (kt + 1 < ntiles) {
         tile(S0 + (kt & 1) * STAGE, S0 + ((kt + 1) & 1) * STAGE, yes_t(), no_t());
@@ -1731,7 +1683,6 @@ __global__ __launch_bounds__(WIDE_THREADS, 2) void lvt_gemm_wide_kernel(const KP
         }
         __syncthreads();
     }
-#ifndef LVT_NO_FAST_EPILOGUE
     if (p.vec_epi && !(p.flags & (LVT_EPI_PLANES | LVT_EPI_ACCUM | LVT_EPI_TANH))) {
         // plain forms (every launch of the transformer): epilogue_fast.h -- same arithmetic, compile-time flag sets, no workgroup
         // barriers, max |C| peeked before the stores
@@ -1751,7 +1702,6 @@ __global__ __launch_bounds__(WIDE_THREADS, 2) void lvt_gemm_wide_kernel(const KP
         if (p.c_amax) lvt_block_amax_commit_seen(am_w, p.c_amax, lds + TURN_FLOATS, seen);
         return;
     }
-#endif
     if (p.vec_epi) lvt_epilogue_vec<AMODE, BM, BN, WM, WN>(p, acc, lds, m0, n0, wm, wn, lane, 0, tc.coff, tc.z, tc.split);
     else lvt_epilogue<AMODE, BM, BN, WM, WN>(p, acc, m0, n0, wm, wn, l31, half, 0, tc.coff, tc.z, tc.split);
 }
@@ -1851,9 +1801,7 @@ __global__ void lvt_pack_weight_parity_kernel(const float *__restrict__ w, float
 // store per element -- 34-48 us for the 75 MB of partials of a 3x3 256-channel layer; this one is bound by reading them.)
 #define UW_CO 64
 #define UW_CI 4
-#ifndef UW_WAVES
 #define UW_WAVES 16                      // (tap, ci) rows in flight per pass: with 4 a CU held 4 waves, each waiting on its own loads
-#endif
 __global__ __launch_bounds__(64 * UW_WAVES) void lvt_unpack_wgrad_tiled_kernel(const float *__restrict__ partial, long long stride,
                                                                                int splits, float *__restrict__ dw, int taps, int Ci,
                                                                                int Co) {
@@ -1996,9 +1944,9 @@ static int launch_tile(const KParams &p, int zcount, hipStream_t s) {
         lvt_set_error("gemm: LVT_EPI_PLANES needs 16-byte aligned bias / res / mask and ldr, ldm %% 4 == 0");
         return LVT_EINVAL;
     }
-    if (math_of(p.flags) == 2 && BK == 32)
+    if (math_of(p.flags) == 2)
         hipLaunchKernelGGL((lvt_gemm_kernel<AMODE, BMODE, BM, BN, WM, WN, 2>), grid, dim3(NTHREADS), 0, s, pv);
-    else if (math_of(p.flags) == 1 && BK == 32)
+    else if (math_of(p.flags) == 1)
         hipLaunchKernelGGL((lvt_gemm_kernel<AMODE, BMODE, BM, BN, WM, WN, 1>), grid, dim3(NTHREADS), 0, s, pv);
     else
         hipLaunchKernelGGL((lvt_gemm_kernel<AMODE, BMODE, BM, BN, WM, WN, 0>), grid, dim3(NTHREADS), 0, s, pv);
@@ -2118,11 +2066,10 @@ extern "C" int lvt_gemm_f32(const lvt_gemm_desc *d, void *workspace, size_t work
         LVT_REQUIRE(!d->a_colsum, "gemm: a_colsum needs splits > 1");
     }
     int rc;
-    static const int no_wide = getenv("LVT_NO_WIDE_GEMM") ? 1 : 0;
     // (the wide kernel addresses its operands with 32-bit byte offsets from a per-batch base: each must span < 4 GB)
     const long long a_span = d->ta ? (long long)d->K * d->lda : (long long)d->M * d->lda + (long long)(d->K / p.a_kb) * d->a_skb;
     const long long b_span = d->tb ? (long long)d->K * d->ldb : (long long)d->N * d->ldb + (long long)(d->K / p.b_kb) * d->b_skb;
-    const bool wide = !no_wide && math_of(d->flags) == 2 && BK == 32 && d->M > 128 && d->K % BK == 0 && p.a_kb % BK == 0 &&
+    const bool wide = math_of(d->flags) == 2 && d->M > 128 && d->K % BK == 0 && p.a_kb % BK == 0 &&
                       p.b_kb % BK == 0 && a_span < (1LL << 30) && b_span < (1LL << 30) &&
                       !(d->flags & (LVT_CAUSAL_KMAX | LVT_CAUSAL_KMIN | LVT_CAUSAL_TILE));
     if (wide && d->ta == 0 && d->tb == 0) rc = launch_wide<0, 0>(p, zc, s);
@@ -2285,8 +2232,7 @@ extern "C" int lvt_conv3d_pack_weight_t(const lvt_conv_geom *g, const float *w, 
 
 // the frame-resident kernel serves 3x3 / stride 1 / pad 1 convolutions of 16x16 frames with Ci % 32 == 0, Co % 128 == 0
 static bool patch_conv_eligible(const lvt_conv_geom *g, int flags) {
-    static const int off = getenv("LVT_NO_PATCH_CONV") ? 1 : 0;
-    return !off && math_of(flags) >= 1 && BK == 32 && g->Kt == 1 && g->Kh == 3 && g->Kw == 3 && g->st == 1 && g->sh == 1 &&
+    return math_of(flags) >= 1 && g->Kt == 1 && g->Kh == 3 && g->Kw == 3 && g->st == 1 && g->sh == 1 &&
            g->sw == 1 && g->pt == 0 && g->ph == 1 && g->pw == 1 && g->Ti == 1 && g->Hi == 16 && g->Wi == 16 && g->To == 1 &&
            g->Ho == 16 && g->Wo == 16 && g->Ci % 32 == 0 && g->Co % 128 == 0;
 }
@@ -2294,8 +2240,7 @@ extern "C" int lvt_conv3d_uses_patch_kernel(const lvt_conv_geom *g, int flags) {
 
 // 4x4 / stride 2 / pad 1 convolution 32x32 -> 16x16 on the frame-resident kernel (parity classes)
 static bool conv2x_eligible(const lvt_conv_geom *g, int flags) {
-    static const int off = (getenv("LVT_NO_PATCH_CONV") || getenv("LVT_NO_PARITY_CONV")) ? 1 : 0;
-    return !off && math_of(flags) >= 1 && BK == 32 && g->Kt == 1 && g->Kh == 4 && g->Kw == 4 && g->st == 1 && g->sh == 2 &&
+    return math_of(flags) >= 1 && g->Kt == 1 && g->Kh == 4 && g->Kw == 4 && g->st == 1 && g->sh == 2 &&
            g->sw == 2 && g->pt == 0 && g->ph == 1 && g->pw == 1 && g->Ti == 1 && g->Hi == 32 && g->Wi == 32 && g->To == 1 &&
            g->Ho == 16 && g->Wo == 16 && g->Ci % 32 == 0 && g->Co % 128 == 0;
 }
@@ -2397,8 +2342,7 @@ extern "C" int lvt_conv3d_fwd(const lvt_conv_geom *g, const float *x, const floa
     {
         // a 1x1x1 / stride 1 / unpadded convolution IS the product x (M x Ci) . wp (Ci x Co): in f16x2 mode it takes the wide
         // pipelined kernel (no im2col index arithmetic in the loader, 256-row tiles)
-        static const int no_wide = getenv("LVT_NO_WIDE_GEMM") ? 1 : 0;
-        if (!no_wide && math_of(flags) == 2 && BK == 32 && g->Kt == 1 && g->Kh == 1 && g->Kw == 1 && g->st == 1 && g->sh == 1 &&
+        if (math_of(flags) == 2 && g->Kt == 1 && g->Kh == 1 && g->Kw == 1 && g->st == 1 && g->sh == 1 &&
             g->sw == 1 && g->pt == 0 && g->ph == 0 && g->pw == 0 && g->Ci % BK == 0 && p.M > 128 && lvt_aligned16(x) && lvt_aligned16(wp) &&
             (long long)p.M * g->Ci < (1LL << 30)) {
             p.lda = g->Ci; p.a_kb = p.K; p.b_kb = p.K;
@@ -2406,17 +2350,13 @@ extern "C" int lvt_conv3d_fwd(const lvt_conv_geom *g, const float *x, const floa
         }
     }
     if (g->Co <= 32) return launch_tile<A_CONV_K, B_NPLAIN, 128, 32, 4, 1>(p, 1, (hipStream_t)stream);
-#ifdef LVT_CX_SMALLK64
-    if (p.K <= 64) return launch_tile<A_CONV_K, B_NPLAIN, 64, 128, 2, 2>(p, 1, (hipStream_t)stream);
-#endif
     return launch_tile<A_CONV_K, B_NPLAIN, 128, 128, 2, 2>(p, 1, (hipStream_t)stream);
 }
 
 // ---- stride-2 transposed convolution of 16x16 frames on the frame-resident kernel -------------------------------------
 static bool convt2x_eligible(const lvt_conv_geom *g, int flags) {
-    static const int off = (getenv("LVT_NO_PATCH_CONV") || getenv("LVT_NO_PHASE_CONV")) ? 1 : 0;
     // g is the geometry of the FORWARD strided convolution (Ci -> Co, 32x32 -> 16x16); the transposed pass maps Co -> Ci
-    return !off && math_of(flags) >= 1 && BK == 32 && g->Kt == 1 && g->Kh == 4 && g->Kw == 4 && g->st == 1 && g->sh == 2 &&
+    return math_of(flags) >= 1 && g->Kt == 1 && g->Kh == 4 && g->Kw == 4 && g->st == 1 && g->sh == 2 &&
            g->sw == 2 && g->pt == 0 && g->ph == 1 && g->pw == 1 && g->Ti == 1 && g->Hi == 32 && g->Wi == 32 && g->To == 1 &&
            g->Ho == 16 && g->Wo == 16 && g->Co % 32 == 0 && g->Ci % 128 == 0;
 }
@@ -2492,8 +2432,7 @@ extern "C" int lvt_conv3d_bwd_data(const lvt_conv_geom *g, const float *dy, cons
     LVT_REQUIRE_AMAX(flags, ax, "conv3d_bwd_data"); set_amax(p, ax);
     {
         // 1x1x1 / stride 1 / unpadded: dx (M x Ci) = dy (M x Co) . wp^T, wp = (Ci x Co) read k-contiguous -- the wide kernel
-        static const int no_wide = getenv("LVT_NO_WIDE_GEMM") ? 1 : 0;
-        if (!no_wide && math_of(flags) == 2 && BK == 32 && g->Kt == 1 && g->Kh == 1 && g->Kw == 1 && g->st == 1 && g->sh == 1 &&
+        if (math_of(flags) == 2 && g->Kt == 1 && g->Kh == 1 && g->Kw == 1 && g->st == 1 && g->sh == 1 &&
             g->sw == 1 && g->pt == 0 && g->ph == 0 && g->pw == 0 && g->Co % BK == 0 && p.M > 128 && lvt_aligned16(dy) && lvt_aligned16(wp) &&
             (long long)p.M * g->Co < (1LL << 30)) {
             p.lda = g->Co; p.ldb = g->Co; p.a_kb = p.K; p.b_kb = p.K;
@@ -2536,12 +2475,10 @@ static void unpack_plain_wgrad(const float *partial, long long stride, int split
 }
 // 1 when lvt_conv3d_bwd_weight also produces the bias gradient (db) for this geometry: every served geometry does (the implicit-
 // GEMM path sums the dy tiles it streams, the frame-resident kernels the dy rows / patches they stage)
-// (LVT_NO_FRAME_BIAS=1: A/B switch -- the frame-resident geometries answer 0 again and callers fall back to lvt_colsum)
 extern "C" int lvt_conv3d_bwd_weight_fuses_bias(const lvt_conv_geom *g, int flags) {
-    static const int off = getenv("LVT_NO_FRAME_BIAS") ? 1 : 0;
     if (!g) return 0;
-    if (flags & LVT_WGRAD_DB_OF_X) return !off && lvt_wgrad_frames_role(g, flags) == 3;      // (the stride-2 frame-resident kernel only)
-    return off && lvt_wgrad_frames_role(g, flags) ? 0 : 1;
+    if (flags & LVT_WGRAD_DB_OF_X) return lvt_wgrad_frames_role(g, flags) == 3;      // (the stride-2 frame-resident kernel only)
+    return 1;
 }
 
 static int bwd_weight_splits(const lvt_conv_geom *g) {

@@ -60,8 +60,6 @@ struct P2Params {
     const float *bias; const float *res; long long ldr; const float *mask; long long ldm;
     const float *a_amax, *b_amax; float *c_amax;
     char *Cp; long long ldcp; const float *cp_amax;     // optional second output: the P2 image of C under the scale of *cp_amax
-    int stagger;                                        // experiment: first-wave workgroups start (id >> 3 & 3) * stagger * 64 cycles late
-    unsigned long long *dbg;                            // P2_X_DBG builds: 4 timestamps per workgroup
 };
 
 // ---- the f16x2 split: identical to gemm_engine.hip (f16_split_pair<2048>, lvt_f16_scale) ----------------------------------
@@ -120,16 +118,6 @@ __global__ __launch_bounds__(P2_THREADS, 2) void lvt_gemm_p2_kernel(const P2Para
     const char *Bk = p.B + (zo * p.sB_o + zi * p.sB_i) * 4;
     const long long coff = zo * p.sC_o + zi * p.sC_i;
 
-#ifdef P2_X_DBG
-#define P2_STAMP(i) do { if (p.dbg && threadIdx.x == 0) p.dbg[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 + (i)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define P2_STAMP(i) do {} while (0)
-#endif
-    P2_STAMP(0);
-    if (p.stagger && blockIdx.y == 0 && blockIdx.x < 256) {
-        const int ph = (blockIdx.x >> 3) & 3;
-        for (int i = 0; i < ph * p.stagger; ++i) __builtin_amdgcn_s_sleep(1);
-    }
     int unscale = 0;
     const float sa = p2_scale(p.a_amax, unscale);
     (void)p2_scale(p.b_amax, unscale);
@@ -183,36 +171,18 @@ __global__ __launch_bounds__(P2_THREADS, 2) void lvt_gemm_p2_kernel(const P2Para
     };
     auto dma_a = [&](int stage) {       // AP == 1
         char *dst = lds + stage * P2_A_STAGE + wave_s * 4096;
-#ifdef P2_X_IMMOFF       // (experiment: one M0 per stage, the chunk through the instruction offset -- it moves BOTH addresses)
-        __builtin_amdgcn_global_load_lds((p2_gl_void *)(Ak + agoff[0]), (p2_lds_void *)dst, 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((p2_gl_void *)(Ak + agoff[1] - 1024), (p2_lds_void *)dst, 16, 1024, 0);
-        __builtin_amdgcn_global_load_lds((p2_gl_void *)(Ak + agoff[2] - 2048), (p2_lds_void *)dst, 16, 2048, 0);
-        __builtin_amdgcn_global_load_lds((p2_gl_void *)(Ak + agoff[3] - 3072), (p2_lds_void *)dst, 16, 3072, 0);
-#else
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             __builtin_amdgcn_global_load_lds((p2_gl_void *)(Ak + agoff[c]), (p2_lds_void *)(dst + c * 1024), 16, 0, 0);
-#ifdef P2_X_NOPS
-            asm volatile("s_nop 7\n\ts_nop 7");
-#endif
         }
-#endif
         Ak += 128;
     };
     auto dma_b = [&](int stage) {
         char *dst = lds + P2_B_BASE + stage * P2_B_STAGE + wave_s * 2048;
-#ifdef P2_X_IMMOFF
-        __builtin_amdgcn_global_load_lds((p2_gl_void *)(Bk + bgoff[0]), (p2_lds_void *)dst, 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((p2_gl_void *)(Bk + bgoff[1] - 1024), (p2_lds_void *)dst, 16, 1024, 0);
-#else
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             __builtin_amdgcn_global_load_lds((p2_gl_void *)(Bk + bgoff[c]), (p2_lds_void *)(dst + c * 1024), 16, 0, 0);
-#ifdef P2_X_NOPS
-            asm volatile("s_nop 7\n\ts_nop 7");
-#endif
         }
-#endif
         Bk += 128;
     };
 
@@ -297,20 +267,13 @@ __global__ __launch_bounds__(P2_THREADS, 2) void lvt_gemm_p2_kernel(const P2Para
         store_a(0);
         if (ntiles > 1) fetch_a();
     }
-    P2_STAMP(1);
     int kt = 0;
-    if (ntiles == 1) { landed(0); __syncthreads(); P2_STAMP(2); }
+    if (ntiles == 1) { landed(0); __syncthreads(); }
     for (; kt + 2 < ntiles; ++kt) {
         landed(kt & 1);
         __syncthreads();                // tile kt has landed (LDS-DMA: vmcnt(0) of every wave, then the barrier); stage (kt + 1) & 1 is free
-#ifdef P2_X_SLEEP
-        __builtin_amdgcn_s_sleep(20); __syncthreads();
-#endif
         if (AP) dma_a((kt + 1) & 1);
         dma_b((kt + 1) & 1);
-#ifdef P2_X_SLEEP2       // (experiment: delay only the compute of tile kt, after the next tile's DMA is issued)
-        __builtin_amdgcn_s_sleep(20);
-#endif
         tile(kt & 1, yes_t(), yes_t());
     }
     if (kt + 1 < ntiles) {
@@ -325,29 +288,19 @@ __global__ __launch_bounds__(P2_THREADS, 2) void lvt_gemm_p2_kernel(const P2Para
     __syncthreads();
     tile(kt & 1, no_t(), no_t());
     __syncthreads();
-    P2_STAMP(3);
-
     lvt_f16x2_finish<TM, TN>(acc, acx, unscale);
 
-    P2_STAMP(4);
     // ---- epilogue.  Plain forms: epilogue_fast.h (no workgroup barrier, compile-time flag sets, max |C| peeked up front)
-#ifndef P2_NO_FAST_EPI
     if (!p.Cp) {
-#ifdef P2_X_EPI_BARRIER
-        __syncthreads();
-#endif
         const unsigned seen = lvt_amax_peek(p.c_amax);
         LvtEpi e;
         e.M = p.M; e.N = p.N; e.C = p.C; e.ldc = p.ldc; e.coff = coff; e.alpha = p.alpha; e.flags = p.flags;
         e.bias = p.bias; e.res = p.res; e.ldr = p.ldr; e.mask = p.mask; e.ldm = p.ldm;
         const float am_w = lvt_epi_fast_dispatch<TM, TN>(e, acc, reinterpret_cast<float *>(lds) + wave * (32 * TN * 32),
                                                          m0 + wm * (TM * 32), n0 + wn * (TN * 32), lane);
-        P2_STAMP(5);
         if (p.c_amax) lvt_block_amax_commit_seen(am_w, p.c_amax, reinterpret_cast<float *>(lds + 8 * 32 * TN * 32 * 4), seen);
-        P2_STAMP(6);
         return;
     }
-#endif
     // ---- epilogue: every wave turns its 64 x 64 sub-tile through LDS 32 rows at a time (lvt_epilogue_vec, gemm_engine.hip):
     // a lane then owns 4 consecutive columns, all global accesses are 16-byte ones
     constexpr int SW = TN * 32, C4 = SW / 4;
@@ -380,11 +333,7 @@ __global__ __launch_bounds__(P2_THREADS, 2) void lvt_gemm_p2_kernel(const P2Para
                     v.x = mk.x > 0.f ? v.x : 0.f; v.y = mk.y > 0.f ? v.y : 0.f; v.z = mk.z > 0.f ? v.z : 0.f; v.w = mk.w > 0.f ? v.w : 0.f;
                 }
                 am = fmaxf(am, fmaxf(fmaxf(lvt_absf(v.x), lvt_absf(v.y)), fmaxf(lvt_absf(v.z), lvt_absf(v.w))));
-#ifndef P2_X_NOSTORE        // (timing experiment: the epilogue without its global stores)
                 *reinterpret_cast<float4 *>(p.C + coff + row * p.ldc + col) = v;
-#else
-                if (v.x == 1.2345e33f) *reinterpret_cast<float4 *>(p.C + coff + row * p.ldc + col) = v;
-#endif
                 if (p.Cp) {
                     uint2 ph, pl;
                     p2_split4(v, cps, ph, pl);
@@ -396,14 +345,8 @@ __global__ __launch_bounds__(P2_THREADS, 2) void lvt_gemm_p2_kernel(const P2Para
         }
         __syncthreads();
     }
-    P2_STAMP(5);
     if (p.c_amax) lvt_block_amax_commit(am, p.c_amax, reinterpret_cast<float *>(lds));
-    P2_STAMP(6);
 }
-#ifdef P2_X_DBG
-static unsigned long long *g_p2_dbg = nullptr;
-extern "C" void lvt_p2_debug_buffer(void *p) { g_p2_dbg = (unsigned long long *)p; }
-#endif
 
 extern "C" int lvt_gemm_p2_f32(const lvt_gemm_p2_desc *d, void *stream) {
     LVT_REQUIRE(d && d->A && d->B && d->C, "gemm_p2: null pointer");
@@ -447,10 +390,6 @@ extern "C" int lvt_gemm_p2_f32(const lvt_gemm_p2_desc *d, void *stream) {
     p.bias = d->bias; p.res = d->res; p.ldr = d->ldr; p.mask = d->mask; p.ldm = d->ldm;
     p.a_amax = d->a_amax; p.b_amax = d->b_amax; p.c_amax = d->c_amax;
     p.Cp = (char *)d->Cp; p.ldcp = d->ldcp; p.cp_amax = d->cp_amax;
-    { static const char *st = getenv("LVT_P2_STAGGER"); p.stagger = st ? atoi(st) : 0; }
-#ifdef P2_X_DBG
-    p.dbg = g_p2_dbg;
-#endif
     dim3 grid((unsigned)(ntm * ntn), (unsigned)zc, 1);
     if (d->a_planes) hipLaunchKernelGGL((lvt_gemm_p2_kernel<1>), grid, dim3(P2_THREADS), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL((lvt_gemm_p2_kernel<0>), grid, dim3(P2_THREADS), 0, (hipStream_t)stream, p);

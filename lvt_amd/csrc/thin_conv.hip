@@ -20,9 +20,7 @@
 // ------------------------------------------------------------------------------------------------
 #define TC_CK 16
 #define TC_LDX 20                       // floats per staged pixel (16 + 4 pad): b128 reads conflict-free
-#ifndef TC_P
 #define TC_P 1                         // positions per thread (rows lh + 8*p)
-#endif
 #define TC_TH (8 * TC_P)
 #define TC_TW 32
 
@@ -270,11 +268,7 @@ __global__ __launch_bounds__(TM_THREADS) void lvt_convt4_mfma_kernel(const float
         for (int c = 0; c < 4; ++c) {
 #pragma unroll
             for (int i = 0; i < NLD; ++i)
-#ifdef TM_X_NOSTAGE      // (timing experiments: the loaded values still have to arrive)
-                if (loff[i] >= 0 && pre[c & 1][i].x == 12345.f) Xp[loff[i]] = 1;
-#else
                 if (loff[i] >= 0) tm_split4(pre[c & 1][i], sx, Xp + loff[i], Xp + TM_XPL + loff[i]);
-#endif
             __syncthreads();                                   // (first pass: the weight planes as well)
             // chunk c + 2 into the registers just stored: chunks 2, 3 of this band, then chunks 0, 1 of the next one
             if (c < 2) fetch(c + 2, pre[c & 1]);
@@ -282,7 +276,6 @@ __global__ __launch_bounds__(TM_THREADS) void lvt_convt4_mfma_kernel(const float
                 if (c == 2) setup(band + gridDim.x, img, h0, w0);
                 fetch(c - 2, pre[c & 1]);
             }
-#ifndef TM_X_NOBLOCK
 #pragma unroll
             for (int nbr = 0; nbr < 9; ++nbr) {
                 const int dh = nbr / 3, dw = nbr - 3 * dh;
@@ -292,16 +285,11 @@ __global__ __launch_bounds__(TM_THREADS) void lvt_convt4_mfma_kernel(const float
                 for (int t = 0; t < 2; ++t) {
                     const unsigned short *ap = Xp + ((wave + dh) * TM_PW + 16 * t + m + dw) * TM_XP + 8 * kq;
                     const tm_f16x8 ah = *reinterpret_cast<const tm_f16x8 *>(ap), al = *reinterpret_cast<const tm_f16x8 *>(ap + TM_XPL);
-#ifdef TM_X_NOMFMA
-                    acc[t][0] += (float)ah[0] + (float)bl[1] + (float)al[2] + (float)bh[3];
-#else
                     acx[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, acx[t], 0, 0, 0);
                     acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc[t], 0, 0, 0);
                     acx[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acx[t], 0, 0, 0);
-#endif
                 }
             }
-#endif
             __syncthreads();                                   // every wave is done with this chunk's patch
         }
         // lane = column (rh, rw, c) of positions (row ch0 + wave, columns cw0 + 16 t + 4 kq + i)
@@ -460,8 +448,7 @@ extern "C" int lvt_convt4_fwd(const float *x, const float *w, const float *bias,
     LVT_REQUIRE(x && w && bias && y && N > 0 && Hi > 0 && Wi > 0, "convT4_fwd: bad args");
     LVT_REQUIRE(Ci % TC_CK == 0 && Cr >= 1 && Cr <= 3, "convT4_fwd: needs Ci %% 16 == 0 and 1..3 output channels");
     LVT_REQUIRE(!(flags & LVT_MATH_F16X2) || (ax && ax->a && ax->b), "convT4_fwd: LVT_MATH_F16X2 needs ax->a = max |x|, ax->b = max |w|");
-    static const int no_mfma = getenv("LVT_NO_CONVT4_MFMA") ? 1 : 0;
-    if ((flags & LVT_MATH_F16X2) && !no_mfma && Ci == TM_CI && Hi % TM_R == 0 && Wi % TM_W == 0 && lvt_aligned16(x) && lvt_aligned16(y) &&
+    if ((flags & LVT_MATH_F16X2) && Ci == TM_CI && Hi % TM_R == 0 && Wi % TM_W == 0 && lvt_aligned16(x) && lvt_aligned16(y) &&
         (long long)N * (Hi / TM_R) * (Wi / TM_W) < 0x7fffffffLL) {
         const long long nbands = (long long)N * (Hi / TM_R) * (Wi / TM_W);
         const unsigned grid = (unsigned)(nbands < LVT_NUM_CU ? nbands : LVT_NUM_CU);       // persistent: one workgroup per CU

@@ -547,9 +547,6 @@ __device__ __forceinline__ float vqf_pow2(int field) { return __uint_as_float((u
 // A strict > keeps the lowest position among equal scores.  POS, POS + 1 are inline constants (0 .. 64).
 template <int POS>
 __device__ __forceinline__ void vqf_select2(float s0, float s1, float &lb, int &lp) {
-#ifdef VQF_X_NOSEL
-    lb = fmaxf(lb, s0 + s1); return;
-#endif
     unsigned long long m0, m1;
     asm("v_cmp_gt_f32_e64 %2, %4, %0\n\t"
         "v_max_f32_e32 %0, %0, %4\n\t"
@@ -681,9 +678,7 @@ __global__ __launch_bounds__(VQ_THREADS) void lvt_vq_nearest_f16x2_kernel(
                 zb[s][1] = __builtin_bit_cast(vqf_h8, ul);
             }
         }
-#ifndef VQF_X_NOROWS
         if (tile + tstride < ntiles) load_rows(tile + tstride);                      // in flight during the scan
-#endif
 
         float best = -INFINITY, lb = 0.f;
         int bidx = 0, lp = 0;
@@ -730,11 +725,7 @@ __global__ __launch_bounds__(VQ_THREADS) void lvt_vq_nearest_f16x2_kernel(
                     accP = __builtin_amdgcn_mfma_f32_32x32x16_f16(afP[G][0], zb[G][0], accP, 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-#ifdef VQF_X_NOFRAG
-                if constexpr (NEXT) if (cn == 0) {
-#else
                 if constexpr (NEXT) {
-#endif
                     afN[G][0] = *reinterpret_cast<const vqf_h8 *>(f0 + 16 * G);
                     afN[G][1] = *reinterpret_cast<const vqf_h8 *>(f1 + 16 * G);
                 }

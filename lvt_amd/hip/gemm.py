@@ -257,8 +257,6 @@ class PackBatch:
     """The weight packs of a whole convolution stack as ONE launch (lvt_conv3d_pack_weights_multi): `plain`, `t`, `phases`,
     `parity` allocate the destination and queue the pack (same layouts and bits as pack_weight*), `launch` issues them."""
 
-    SINGLE = bool(os.environ.get("LVT_NO_PACK_BATCH"))        # A/B switch: one launch per pack, as before round 4
-
     # f16x2: the packs that a frame-resident launch will read also get their tiles as ready LDS images, right behind the fp32
     # pack in the same buffer (lvt_conv3d_weight_images, one more launch per stack); the conv wrappers below then pass
     # CONV_WEIGHT_IMAGE and the kernel stages the weight tiles by LDS-DMA.  LVT_NO_WEIGHT_IMAGES=1: the in-kernel split (A/B switch).
@@ -268,8 +266,6 @@ class PackBatch:
         self.entries, self.keep, self.images = [], [], []
 
     def _add(self, kind, g, w, Ci_real, Co_real, shape, taps, image=False):
-        if self.SINGLE:
-            return (pack_weight, pack_weight_t, pack_weight_phases, pack_weight_parity)[kind](g, w, Ci_real, Co_real)
         L.require(w)
         n = 1
         for d in shape:

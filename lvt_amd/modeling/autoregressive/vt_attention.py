@@ -189,7 +189,6 @@ def linear_wgrad_pair(dy0, x0, dy1, x1, n_out, k_in, rows):
     return dw, db
 
 
-CAUSAL_SKIP = not os.environ.get("LVT_NO_CAUSAL_SKIP")      # A/B switch of the causal reductions in the backward products
 FUSED_ATTENTION = True      # scores + bias + mask + softmax + P.V in one launch when the block is 256 tokens x 128 dims
 # q / k / v / dO as bf16x3 planes into the pipelined attention kernels (csrc/attention_pipe.hip): forward and the whole core
 # backward (dQ, dK, dV, bank gradients) as three fused launches on 16-wide tiles (eight waves per workgroup, two per SIMD):
@@ -202,7 +201,6 @@ PLANE_ATTENTION = None
 # straight from the projection GEMMs (no planes), no attention matrix in HBM (two floats per row are saved instead of 256),
 # P and dS recomputed in the backward pass.  LVT_NO_FLASH_ATTENTION=1 (or FLASH_ATTENTION = False) keeps the plane kernels.
 FLASH_ATTENTION = None
-PAIR_FFN_WGRAD = not os.environ.get("LVT_NO_PAIR_WGRAD")     # the two FFN weight gradients of a layer as one 2-batch launch
 
 
 def _use_flash(S, da, block, pairs):
@@ -309,7 +307,7 @@ class _BlockLocalAttentionFn(torch.autograd.Function):
         G.gemm(dy2, f3w, dh1, M, dff, d, ta=0, tb=1, ldb=dff, flags=L.EPI_MASK, mask=h1)
         dfn = torch.empty(M, d, dtype=torch.float32, device=dev)
         G.gemm(dh1, f1w, dfn, M, d, dff, ta=0, tb=1, ldb=d)
-        if d == dff and PAIR_FFN_WGRAD:
+        if d == dff:
             # both FFN weight gradients are (d x d) = dy^T x products over the same rows: one launch
             dwp, dbp = linear_wgrad_pair(dy2, h1, dh1, fn, d, dff, M)
             df3w, df3b, df1w, df1b = dwp[0], dbp[0], dwp[1], dbp[1]
@@ -345,17 +343,16 @@ class _BlockLocalAttentionFn(torch.autograd.Function):
         dq, dk, dv = dqkv[0], dqkv[1], dqkv[2]
         # masked (causal) layers: P and dS vanish above the diagonal (the forward kernel writes exact zeros there), so the
         # products below skip the structurally-zero part of their reductions / tiles
-        cz = ctx.masked and CAUSAL_SKIP
         G.gemm(P, do, dv, S, da, S, ta=1, tb=1, lda=S, ldb=hd, ldc=hd, sA=(na * S * S, S * S), sB=(S * hd, da),
-               sC=(S * hd, da), flags=L.CAUSAL_KMIN if cz else 0, **bh)              # dV[j] = sum_{i >= j} P[i][j] dO[i]
+               sC=(S * hd, da), flags=L.CAUSAL_KMIN if ctx.masked else 0, **bh)            # dV[j] = sum_{i >= j} P[i][j] dO[i]
         dP = torch.empty(b, na, S, S, dtype=torch.float32, device=dev)
         G.gemm(do, v, dP, S, S, da, ta=0, tb=0, lda=hd, ldb=hd, ldc=S, sA=(S * hd, da), sB=(S * hd, da),
-               sC=(na * S * S, S * S), flags=L.CAUSAL_TILE if cz else 0, **bh)       # dP[i][j] only matters for j <= i
+               sC=(na * S * S, S * S), flags=L.CAUSAL_TILE if ctx.masked else 0, **bh)     # dP[i][j] only matters for j <= i
         ddt, ddh, ddw = tx.attn_softmax_bwd_(P, dP, temper, ctx.block)       # dP now holds dS
         G.gemm(dP, k, dq, S, da, S, ta=0, tb=1, lda=S, ldb=hd, ldc=hd, sA=(na * S * S, S * S), sB=(S * hd, da),
-               sC=(S * hd, da), flags=L.CAUSAL_KMAX if cz else 0, **bh)              # dQ[i] = sum_{j <= i} dS[i][j] K[j]
+               sC=(S * hd, da), flags=L.CAUSAL_KMAX if ctx.masked else 0, **bh)            # dQ[i] = sum_{j <= i} dS[i][j] K[j]
         G.gemm(dP, q, dk, S, da, S, ta=1, tb=1, lda=S, ldb=hd, ldc=hd, sA=(na * S * S, S * S), sB=(S * hd, da),
-               sC=(S * hd, da), flags=L.CAUSAL_KMIN if cz else 0, **bh)              # dK[j] = sum_{i >= j} dS[i][j] Q[i]
+               sC=(S * hd, da), flags=L.CAUSAL_KMIN if ctx.masked else 0, **bh)            # dK[j] = sum_{i >= j} dS[i][j] Q[i]
         del dP
         return _BlockLocalAttentionFn._finish_backward(ctx, dqkv, ddt, ddh, ddw, dy1, dproj, df0w, df0b, df1w, df1b, df3w, df3b)
 
