@@ -33,7 +33,7 @@ extern "C" {
 #define LVT_ENODEVICE   (-4)   /* no gfx950 device visible                             */
 
 const char *lvt_last_error(void);
-int lvt_version(void);          /* 610 = round 6 (ABI changes are listed in INTEGRATION.md) */
+int lvt_version(void);          /* 620 = generic VQ geometry (ABI changes are listed in INTEGRATION.md) */
 /* Device probe: name, CU count, clock (kHz), HBM bytes.  Returns LVT_ENODEVICE without a GPU. */
 int lvt_device_info(char *name, int name_len, int *cus, int *clock_khz, long long *hbm_bytes);
 
@@ -83,6 +83,9 @@ int lvt_amax_merge(const float *a, const float *b, float *out, void *stream);
 /* lvt_vq_nearest only: coarse-then-exact search (one bf16 MFMA pass + exact re-evaluation of the codes inside the error band;
  * same exact argmin).  Faster on well-separated codebooks, slower on degenerate ones: opt-in, see csrc/vq.hip.            */
 #define LVT_VQ_COARSE  (1 << 17)
+/* lvt_vq_nearest only: take the generic search (see lvt_vq_nearest) even on an instantiated geometry.  For tests and A/B
+ * measurements; the Python side never sets it by default.                                                                */
+#define LVT_VQ_GENERIC (1 << 22)
 
 /* ---- epilogue flags shared by GEMM / conv ------------------------------------------------------ */
 #define LVT_EPI_BIAS        1   /* + bias[n]                                                  */
@@ -326,22 +329,32 @@ int lvt_colsum(const float *g, long long M, int N, long long ld, float *out, voi
  *     per-half (distance, index) candidates go through `workspace`;
  *   LVT_MATH_F32, or bf16x3 without a workspace: the fp32-MFMA kernel with the whole codebook LDS-resident.
  * All three agree with an fp64 search wherever the top-2 distance gap exceeds 1e-5 (|x|^2 + max |e|^2); which code a closer
- * pair resolves to is an artefact of the fp32 evaluation order in the reference as well.                       */
+ * pair resolves to is an artefact of the fp32 evaluation order in the reference as well.
+ * Geometry: the kernels above are instantiated for D == 64 and KC in {128, 256, 512}.  Any other D (multiple of 16,
+ * 16..256) and KC (multiple of 64, 64..2048) -- or any call carrying LVT_VQ_GENERIC -- takes the generic search
+ * (argmax_k x.e_k - |e_k|^2 / 2, the codebook streamed through LDS in code tiles, lowest k on ties): f16x2 arithmetic under
+ * LVT_MATH_F16X2, exact fp32 MFMAs otherwise (bf16x3 included).  It needs a 256-byte aligned workspace of
+ * lvt_vq_nearest_generic_workspace_bytes(num, D, KC) bytes (the codebook's norms and fp16 planes, made per call); a
+ * geometry outside that set is refused with LVT_EINVAL.                                                        */
 size_t lvt_vq_nearest_workspace_bytes(long long rows, int num, int KC);
+size_t lvt_vq_nearest_generic_workspace_bytes(int num, int D, int KC);
 int lvt_vq_nearest(const float *z, long long rows, int ldz, int num, int D, int KC,
                    const float *codebooks, long long *idx, int P, int flags, void *workspace, size_t workspace_bytes,
                    void *stream);
-/* out[row][g*D+d] = codebooks[g][idx][d]   (index_select / embedding: z_q_st, z_q_bar, mode "emb")   */
+/* out[row][g*D+d] = codebooks[g][idx][d]   (index_select / embedding: z_q_st, z_q_bar, mode "emb"); any D % 4 == 0, any KC */
 int lvt_vq_gather(const long long *idx, const float *codebooks, long long rows, int num, int D, int KC,
                   int P, float *out, int ldo, void *stream);
 /* stats[num][KC][D+1]: per-code sum of assigned rows and (last column) their count.  LDS-private
  * accumulation per (group, row chunk) + fixed-order chunk reduction: no atomics, bit-reproducible.
- * Kept separate from finalize so that a data-parallel all-reduce of `stats` can sit in between.      */
+ * Kept separate from finalize so that a data-parallel all-reduce of `stats` can sit in between.
+ * D == 64 with KC in {128, 256, 512}: one accumulator per (group, chunk); any other D % 4 == 0 up to 256 and KC up to 2048:
+ * one accumulator per (group, code range, chunk), same order and reproducibility.                    */
 size_t lvt_vq_ema_workspace_bytes(long long rows, int num, int D, int KC);
 int lvt_vq_ema_accumulate(const long long *idx, const float *z, long long rows, int ldz, int num, int D,
                           int KC, int P, float *stats, void *workspace, size_t workspace_bytes,
                           void *stream);
-/* running_size[num][KC], running_sum/weight[num][KC][D] updated in place (vq_embedding.py:48-59).    */
+/* running_size[num][KC], running_sum/weight[num][KC][D] updated in place (vq_embedding.py:48-59).
+ * D == 64: any KC; other D up to 256: KC up to 2048.                                                 */
 int lvt_vq_ema_finalize(const float *stats, int num, int D, int KC, float decay, float eps,
                         float *running_size, float *running_sum, float *weight, void *stream);
 
@@ -481,7 +494,7 @@ int lvt_decode_commit(const long long *drawn, int rows, int S1, long long *codes
 
 /* categorical draw per row from logits / temp with caller-supplied uniforms u[row] in [0,1) (the reference draws
  * with torch.multinomial on softmax(logit / temp), videotransformer.py:176-181): code = #{ j : cdf_j <= u * total },
- * clamped to V-1, written as int64 at out[row * out_stride]; `probs` (rows, V) is optional.  V <= 1024.
+ * clamped to V-1, written as int64 at out[row * out_stride]; `probs` (rows, V) is optional.  V <= 2048.
  * With `pos` != NULL the uniforms are read at u + pos[0]*u_pos: a table of draws for every position of a slice,
  * filled once per slice, indexed by the device-side cursor of the decode graphs (no generator inside a graph).  */
 int lvt_sample_categorical(const float *logits, long long rows, int V, float temp, const float *u,

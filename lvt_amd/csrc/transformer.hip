@@ -704,27 +704,28 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void lvt_attn_decode_kernel(const f
 // ------------------------------------------------------------------------------------------------
 // categorical draw from logits with a caller-supplied uniform (videotransformer.py:176-181: softmax(logit / temp)
 // followed by torch.multinomial; here the inverse-CDF rule of oracle.multinomial_from_uniform so that a draw is a
-// pure function of (logits, u)): code = #{ j : cdf_j <= u * total }, clamped to V-1.  One wave per row, V <= 1024.
+// pure function of (logits, u)): code = #{ j : cdf_j <= u * total }, clamped to V-1.  One wave per row, V <= 2048
+// (V <= 1024: lvt_sample_categorical_kernel, 16 elements per lane; V <= 2048: the _wide instantiation, 32 per lane).
 // The code is written as int64 at out[row * out_stride]; probabilities (row, V) are optional.
 // ------------------------------------------------------------------------------------------------
 #define SMP_MAXPER 16
-__global__ __launch_bounds__(64) void lvt_sample_categorical_kernel(const float *__restrict__ logits, int V, float inv_temp,
-                                                                    const float *__restrict__ u, long long *__restrict__ out,
-                                                                    long long out_stride, float *__restrict__ probs,
-                                                                    const int *__restrict__ pos, long long u_pos) {
+template <int MAXPER>
+__device__ __forceinline__ void smp_row(const float *__restrict__ logits, int V, float inv_temp, const float *__restrict__ u,
+                                        long long *__restrict__ out, long long out_stride, float *__restrict__ probs,
+                                        const int *__restrict__ pos, long long u_pos) {
     const int row = blockIdx.x, lane = threadIdx.x;
     if (pos) u += (long long)pos[0] * u_pos;
     const float *x = logits + (long long)row * V;
     const int per = (V + 63) / 64;                      // consecutive elements per lane: cdf order == memory order
     const int j0 = lane * per;
-    float e[SMP_MAXPER];
+    float e[MAXPER];
     float m = -3.4e38f;
 #pragma unroll
-    for (int i = 0; i < SMP_MAXPER; ++i) { e[i] = (i < per && j0 + i < V) ? x[j0 + i] * inv_temp : -3.4e38f; m = fmaxf(m, e[i]); }
+    for (int i = 0; i < MAXPER; ++i) { e[i] = (i < per && j0 + i < V) ? x[j0 + i] * inv_temp : -3.4e38f; m = fmaxf(m, e[i]); }
     m = wmax(m);
     float loc = 0.f;
 #pragma unroll
-    for (int i = 0; i < SMP_MAXPER; ++i) { e[i] = (i < per && j0 + i < V) ? expf(e[i] - m) : 0.f; loc += e[i]; }
+    for (int i = 0; i < MAXPER; ++i) { e[i] = (i < per && j0 + i < V) ? expf(e[i] - m) : 0.f; loc += e[i]; }
     // exclusive scan of the lane sums
     float incl = loc;
 #pragma unroll
@@ -734,19 +735,37 @@ __global__ __launch_bounds__(64) void lvt_sample_categorical_kernel(const float 
     float c = incl - loc;
     int cnt = 0;
 #pragma unroll
-    for (int i = 0; i < SMP_MAXPER; ++i) { c += e[i]; if (i < per && j0 + i < V && c <= thr) ++cnt; }
+    for (int i = 0; i < MAXPER; ++i) { c += e[i]; if (i < per && j0 + i < V && c <= thr) ++cnt; }
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
     if (lane == 0) out[row * out_stride] = cnt < V - 1 ? cnt : V - 1;
     if (probs)
 #pragma unroll
-        for (int i = 0; i < SMP_MAXPER; ++i) if (i < per && j0 + i < V) probs[(long long)row * V + j0 + i] = e[i] / total;
+        for (int i = 0; i < MAXPER; ++i) if (i < per && j0 + i < V) probs[(long long)row * V + j0 + i] = e[i] / total;
+}
+__global__ __launch_bounds__(64) void lvt_sample_categorical_kernel(const float *__restrict__ logits, int V, float inv_temp,
+                                                                    const float *__restrict__ u, long long *__restrict__ out,
+                                                                    long long out_stride, float *__restrict__ probs,
+                                                                    const int *__restrict__ pos, long long u_pos) {
+    smp_row<SMP_MAXPER>(logits, V, inv_temp, u, out, out_stride, probs, pos, u_pos);
+}
+__global__ __launch_bounds__(64) void lvt_sample_categorical_wide_kernel(const float *__restrict__ logits, int V, float inv_temp,
+                                                                         const float *__restrict__ u, long long *__restrict__ out,
+                                                                         long long out_stride, float *__restrict__ probs,
+                                                                         const int *__restrict__ pos, long long u_pos) {
+    smp_row<2 * SMP_MAXPER>(logits, V, inv_temp, u, out, out_stride, probs, pos, u_pos);
 }
 
 extern "C" int lvt_sample_categorical(const float *logits, long long rows, int V, float temp, const float *u,
                                       long long *out, long long out_stride, float *probs, const int *pos, long long u_pos,
                                       void *stream) {
-    LVT_REQUIRE(logits && u && out && rows > 0 && V > 0 && V <= 64 * SMP_MAXPER && temp > 0.f, "sample_categorical: bad args");
+    LVT_REQUIRE(logits && u && out && rows > 0 && V > 0 && V <= 128 * SMP_MAXPER && temp > 0.f, "sample_categorical: bad args");
+    if (V > 64 * SMP_MAXPER) {
+        hipLaunchKernelGGL(lvt_sample_categorical_wide_kernel, dim3((unsigned)rows), dim3(64), 0, (hipStream_t)stream, logits, V,
+                           1.f / temp, u, out, out_stride, probs, pos, u_pos);
+        LVT_CHECK_LAUNCH("lvt_sample_categorical_wide_kernel");
+        return LVT_OK;
+    }
     hipLaunchKernelGGL(lvt_sample_categorical_kernel, dim3((unsigned)rows), dim3(64), 0, (hipStream_t)stream, logits, V,
                        1.f / temp, u, out, out_stride, probs, pos, u_pos);
     LVT_CHECK_LAUNCH("lvt_sample_categorical_kernel");

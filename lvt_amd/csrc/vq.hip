@@ -938,6 +938,578 @@ __global__ __launch_bounds__(512) void lvt_vq_ema_finalize_kernel(const float *_
     }
 }
 
+// ================================================================================================
+// GENERIC GEOMETRY: any sub-vector width D = 16 .. 256 (multiple of 16) and codebook size KC = 64 .. 2048 (multiple of 64).
+// The kernels above stay the route of D == 64, KC in {128, 256, 512}; everything else (and LVT_VQ_GENERIC) comes here.
+//
+// Search.  A whole codebook group no longer fits in LDS (2048 x 64 or 1024 x 256 as two fp16 planes are 512 KB), so the
+// roles turn round: a workgroup of 8 waves owns 256 rows (4 waves / 128 rows from D = 176 on, see below) -- ONE 32-row tile
+// per wave, resident in VGPRs for the whole scan, z read once -- and streams the codebook group through LDS in code tiles of KT codes, double-buffered (tile t + 1 is
+// fetched into registers while tile t is scanned and written to the other buffer behind the scan; one barrier per tile).
+// Every lane keeps its running (max, argmax) in registers across tiles; the codes a lane sees ascend with (tile, 32-code
+// sub-tile, register), so a strict > keeps the lowest index on exact ties across tiles too, and the one exchange between
+// the half-waves at the end takes the lower index of equal scores.  No rows x KC score matrix goes to HBM.
+//   f16x2 (LVT_MATH_F16X2): the arithmetic of lvt_vq_nearest_f16x2_kernel -- argmax_k x.e_k - |e_k|^2 / 2, codebook group as
+//     two fp16 planes under one power-of-two scale sE per group, every row as two planes under its own scale sx, three
+//     v_mfma_f32_32x32x16_f16 per 16 dims (lo hi, hi lo, hi hi).  The planes, -|e|^2 sE / 2 and the group's sE are made
+//     ONCE per call by two small prep kernels into the workspace, so the scan only copies 16-byte chunks into LDS.
+//     LDS tile: [2 planes][KT][D + 8] fp16 + KT floats; the row stride (D + 8) * 2 B is an odd multiple of 16 B for every
+//     D = 16 m, so the 16-byte fragment reads (ds_read_b128, four 16-lane groups) are conflict-free.
+//     KT = 32 * floor(40 KB / (4 (D + 8) + 4) / 32): 384 codes at D = 16, 128 at D = 64, 32 at D = 256; two buffers <= 80 KB,
+//     two workgroups per CU.  Registers: the row tile is D / 2 dwords per lane (hi and lo of D / 2 dims: 128 VGPRs at
+//     D = 256), one accumulator (16), the fragments of one step (8) and the staging registers of the next tile (16 B per
+//     16-byte chunk, 3-8 chunks).  hipcc: 66 VGPRs at D = 16, 90 at D = 64, 124 at D = 128 (4 waves / SIMD), 238 at D = 160
+//     (2); from D = 176 the unrolled scan needs more than the 256 registers of 2 waves per SIMD (it spilled at 512 threads), so
+//     those widths run 4-wave workgroups with up to 512 registers (256 VGPRs + 16-71 AGPRs at D >= 176, 1 wave per SIMD); a
+//     wave still holds all 32 rows x D dims, the dims are not split.  The staging array of the next tile is kept in scratch by
+//     hipcc (16 B per chunk + 16 B per lane: 64 B at D = 16, 80 B at D = 64, 144 B at D = 256; the f32 form and
+//     lvt_vq_nearest_f16x2_kernel have none): a scratch store and load per chunk and tile, not yet removed.
+//   f32 (LVT_MATH_F32), and bf16x3 (neither flag; it takes the f32 form here): v_mfma_f32_32x32x2_f32, exact fp32 products,
+//     score = x.e - |e|^2 / 2.  LDS tile [D][KT + 1] fp32 ([dim][code]: the 32 lanes of a half-wave read 32 consecutive codes,
+//     conflict-free for ds_read_b32) + KT floats, KT = 32 floor((10240 - D) / (D + 1) / 32) capped at 512: 512 at D = 16, 128
+//     at D = 64, 32 at D = 256 (<= 80 KB for two buffers); 95-155 VGPRs up to D = 128, 256 + 45-146 AGPRs from D = 176.  A lane holds dims
+//     (D / 2) half .. + D / 2 - 1 of its row (128 VGPRs at D = 256) and a running (max, argmax) of 16 rows for its code column;
+//     five shuffle steps finish the row reduction.
+//
+// EMA statistics.  The LDS-private accumulator of lvt_vq_ema_partial_kernel cannot hold KC x (D + 1) floats any more, so a
+// workgroup owns (group, code range [k0, k0 + Kt), row chunk) with Kt = 64 * floor(72 KB / (4 (D + 1)) / 64) (1024 codes
+// at D = 16, 256 at D = 64, 64 at D = 256) beside a 64-row staging tile (64 D floats).  It reads the chunk's indices and
+// only the z rows whose code lies in its range: z is still read once in all, the index traffic repeats per code range.
+// Same fixed order as the specialised kernel (rows ascending inside a tile, tiles ascending, chunk partials summed in chunk
+// order by lvt_vq_ema_reduce_kernel): deterministic, atomic-free, bit-reproducible.
+// ================================================================================================
+#define VQG_TILE_BYTES 40960                 // one LDS code tile (two are resident: <= 80 KB, two workgroups per CU)
+// 8 waves per workgroup; 4 from D = 176 on, where a wave needs more than the 256 registers of 2 waves per SIMD
+template <int DG> constexpr int vqg_threads() { return DG >= 176 ? 256 : 512; }
+
+template <int DG> struct VqgF16 {
+    static constexpr int LD = DG + 8;                                                 // plane row stride, fp16
+    static constexpr int KT = (VQG_TILE_BYTES / (4 * LD + 4)) / 32 * 32;             // codes per tile
+    static constexpr int PL = KT * LD;                                                // one plane of one tile, fp16
+    static constexpr int BUF = 4 * PL + 4 * KT;                                       // bytes: hi, lo, -|e|^2 sE / 2
+};
+template <int DG> struct VqgF32 {
+    static constexpr int KT = ((VQG_TILE_BYTES / 4 - DG) / (DG + 1)) / 32 * 32 < 512 ? ((VQG_TILE_BYTES / 4 - DG) / (DG + 1)) / 32 * 32 : 512;
+    static constexpr int LDC = KT + 1;                                                // [dim][code] row stride, fp32
+    static constexpr int BUF = 4 * (DG * LDC + KT);                                   // bytes: codes, -|e|^2 / 2
+};
+
+// per code: |e|^2 (fp32 FMA chain, dims ascending) and max |e|
+__global__ __launch_bounds__(256) void lvt_vq_gen_norms_kernel(const float *__restrict__ codebooks, int KC, int D,
+                                                               float *__restrict__ nrm, float *__restrict__ emax) {
+    const int g = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= KC) return;
+    const float *e = codebooks + ((long long)g * KC + k) * D;
+    float s = 0.f, m = 0.f;
+#pragma unroll 4
+    for (int d = 0; d < D; d += 4) {
+        const float4 v = *reinterpret_cast<const float4 *>(e + d);
+        s = fmaf(v.x, v.x, s); s = fmaf(v.y, v.y, s); s = fmaf(v.z, v.z, s); s = fmaf(v.w, v.w, s);
+        m = fmaxf(m, vqf_absmax4(v));
+    }
+    nrm[(long long)g * KC + k] = s;
+    emax[(long long)g * KC + k] = m;
+}
+
+// the f16x2 operand of a codebook group: sE from the group's max |e| (max |e| sE in [2^14, 2^15)), hi / lo planes [KC][D],
+// hcb = -|e|^2 sE / 2; gsc[g] = {sE, max |hcb|}.  Every workgroup reduces the group's KC maxima itself (<= 16 KB from L2).
+__global__ __launch_bounds__(256) void lvt_vq_gen_planes_kernel(const float *__restrict__ codebooks, int KC, int D,
+                                                                const float *__restrict__ nrm, const float *__restrict__ emax,
+                                                                unsigned short *__restrict__ hi, unsigned short *__restrict__ lo,
+                                                                float *__restrict__ hcb, float *__restrict__ gsc) {
+    __shared__ float red[2][4];
+    const int g = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float *em = emax + (long long)g * KC, *nr = nrm + (long long)g * KC;
+    float m = 0.f, n = 0.f;
+    for (int k = tid; k < KC; k += 256) { m = fmaxf(m, em[k]); n = fmaxf(n, nr[k]); }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { m = fmaxf(m, __shfl_xor(m, o)); n = fmaxf(n, __shfl_xor(n, o)); }
+    if (lane == 0) { red[0][wave] = m; red[1][wave] = n; }
+    __syncthreads();
+    m = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
+    n = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
+    const float sE = vqf_pow2(268 - vqf_ebits(m));
+    if (blockIdx.x == 0 && tid == 0) { gsc[2 * g] = sE; gsc[2 * g + 1] = 0.5f * n * sE; }
+    const long long nq = (long long)KC * D / 4, base = (long long)g * nq;
+    for (long long q = (long long)blockIdx.x * 256 + tid; q < nq; q += (long long)gridDim.x * 256) {
+        const float4 v = *reinterpret_cast<const float4 *>(codebooks + 4 * (base + q));
+        uint2 h, l;
+        vqf_split_pair(v.x, v.y, sE, h.x, l.x);
+        vqf_split_pair(v.z, v.w, sE, h.y, l.y);
+        *reinterpret_cast<uint2 *>(hi + 4 * (base + q)) = h;
+        *reinterpret_cast<uint2 *>(lo + 4 * (base + q)) = l;
+    }
+    for (int k = blockIdx.x * 256 + tid; k < KC; k += gridDim.x * 256) hcb[(long long)g * KC + k] = -0.5f * nr[k] * sE;
+}
+
+template <int DG>
+__global__ __launch_bounds__(vqg_threads<DG>()) void lvt_vq_nearest_gen_f16x2_kernel(
+    const float *__restrict__ z, long long rows, int ldz, int KC, const unsigned short *__restrict__ hi_g,
+    const unsigned short *__restrict__ lo_g, const float *__restrict__ hcb_g, const float *__restrict__ gsc,
+    long long *__restrict__ idx_out, int P, int num) {
+    using T = VqgF16<DG>;
+    constexpr int VQG_THREADS = vqg_threads<DG>();
+    constexpr int NS = DG / 16, LD = T::LD, KT = T::KT, PL = T::PL, BUF = T::BUF;
+    constexpr int CPR = DG / 8;                                                       // 16-byte chunks per code row of a plane
+    constexpr int NCH = 2 * KT * CPR;                                                 // chunks per tile (both planes)
+    constexpr int CH = (NCH + VQG_THREADS - 1) / VQG_THREADS;
+    static_assert(KT >= 32 && KT <= VQG_THREADS, "code tile");
+    extern __shared__ __attribute__((aligned(16))) unsigned char vqg_raw[];
+    const int g = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l31 = lane & 31, half = lane >> 5;
+    const unsigned short *Hg = hi_g + (long long)g * KC * DG, *Lg = lo_g + (long long)g * KC * DG;
+    const float *HCg = hcb_g + (long long)g * KC;
+    // a row's scale is capped so that |e|^2 sE sx / 2 stays below 2^100 (as in lvt_vq_nearest_f16x2_kernel)
+    const int sx_cap = 353 - vqf_ebits(gsc[2 * g + 1]);
+    const int ntl = (KC + KT - 1) / KT;
+
+    uint4 st[CH];
+    float hv = 0.f;
+    auto fetch = [&](int t) {
+        const int k0 = t * KT, nc = KC - k0 < KT ? KC - k0 : KT;
+#pragma unroll
+        for (int i = 0; i < CH; ++i) {
+            const int c = tid + i * VQG_THREADS, pl = c / (KT * CPR), rem = c % (KT * CPR), code = rem / CPR, q = rem % CPR;
+            if (c < NCH && code < nc)
+                st[i] = *reinterpret_cast<const uint4 *>((pl ? Lg : Hg) + (long long)(k0 + code) * DG + 8 * q);
+        }
+        if (tid < nc) hv = HCg[k0 + tid];                                              // (KT <= threads)
+    };
+    auto put = [&](int t, int b) {
+        const int nc = KC - t * KT < KT ? KC - t * KT : KT;
+        unsigned short *pb = reinterpret_cast<unsigned short *>(vqg_raw + b * BUF);
+#pragma unroll
+        for (int i = 0; i < CH; ++i) {
+            const int c = tid + i * VQG_THREADS, pl = c / (KT * CPR), rem = c % (KT * CPR), code = rem / CPR, q = rem % CPR;
+            if (c < NCH && code < nc) *reinterpret_cast<uint4 *>(pb + pl * PL + code * LD + 8 * q) = st[i];
+        }
+        if (tid < nc) reinterpret_cast<float *>(pb + 2 * PL)[tid] = hv;
+    };
+    fetch(0);
+
+    // the wave's row tile: lane holds dims 16 s + 8 half .. + 7 of row tile * 32 + l31 (the B operand layout of the NS steps);
+    // rows past the end are clamped to the last row: their columns are computed and not stored
+    const long long row = ((long long)blockIdx.x * (VQG_THREADS / 64) + wave) * 32 + l31;
+    vqf_h8 zb[NS][2];
+    float sx;
+    {
+        const float *zp = z + (row < rows ? row : rows - 1) * (long long)ldz + (long long)g * DG + 8 * half;
+        float4 raw[2 * NS];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            raw[2 * s] = *reinterpret_cast<const float4 *>(zp + 16 * s);
+            raw[2 * s + 1] = *reinterpret_cast<const float4 *>(zp + 16 * s + 4);
+        }
+        float xm = 0.f;
+#pragma unroll
+        for (int u = 0; u < 2 * NS; ++u) xm = fmaxf(xm, vqf_absmax4(raw[u]));
+        xm = fmaxf(xm, __shfl_xor(xm, 32));
+        const int f = 268 - vqf_ebits(xm);
+        sx = vqf_pow2(f < sx_cap ? f : sx_cap);
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            vqf_u4 uh, ul;
+            unsigned a, b;
+            vqf_split_pair(raw[2 * s].x, raw[2 * s].y, sx, a, b); uh[0] = a; ul[0] = b;
+            vqf_split_pair(raw[2 * s].z, raw[2 * s].w, sx, a, b); uh[1] = a; ul[1] = b;
+            vqf_split_pair(raw[2 * s + 1].x, raw[2 * s + 1].y, sx, a, b); uh[2] = a; ul[2] = b;
+            vqf_split_pair(raw[2 * s + 1].z, raw[2 * s + 1].w, sx, a, b); uh[3] = a; ul[3] = b;
+            zb[s][0] = __builtin_bit_cast(vqf_h8, uh);
+            zb[s][1] = __builtin_bit_cast(vqf_h8, ul);
+        }
+    }
+    put(0, 0);
+    __syncthreads();
+
+    float best = -INFINITY;
+    int bidx = 0;
+    for (int t = 0; t < ntl; ++t) {
+        if (t + 1 < ntl) fetch(t + 1);                                                 // in flight during the scan of tile t
+        const unsigned short *pb = reinterpret_cast<const unsigned short *>(vqg_raw + (t & 1) * BUF);
+        const float *hb = reinterpret_cast<const float *>(pb + 2 * PL) + 4 * half;
+        const int nst = (KC - t * KT < KT ? KC - t * KT : KT) / 32;
+        for (int ct = 0; ct < nst; ++ct) {
+            const unsigned short *f0 = pb + (ct * 32 + l31) * LD + 8 * half, *f1 = f0 + PL;
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {                                             // smallest terms first: lo hi, hi lo, hi hi
+                const vqf_h8 ah = *reinterpret_cast<const vqf_h8 *>(f0 + 16 * s);
+                const vqf_h8 al = *reinterpret_cast<const vqf_h8 *>(f1 + 16 * s);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, zb[s][0], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, zb[s][1], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, zb[s][0], acc, 0, 0, 0);
+            }
+            // accumulator register 4 q + e <-> code 8 q + e + 4 half of the sub-tile: ascending per lane
+            const int cbase = t * KT + ct * 32 + 4 * half;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float4 h4 = *reinterpret_cast<const float4 *>(hb + ct * 32 + 8 * q);
+                const float s0 = fmaf(h4.x, sx, acc[4 * q]), s1 = fmaf(h4.y, sx, acc[4 * q + 1]);
+                const float s2 = fmaf(h4.z, sx, acc[4 * q + 2]), s3 = fmaf(h4.w, sx, acc[4 * q + 3]);
+                if (s0 > best) { best = s0; bidx = cbase + 8 * q; }
+                if (s1 > best) { best = s1; bidx = cbase + 8 * q + 1; }
+                if (s2 > best) { best = s2; bidx = cbase + 8 * q + 2; }
+                if (s3 > best) { best = s3; bidx = cbase + 8 * q + 3; }
+            }
+        }
+        if (t + 1 < ntl) put(t + 1, (t + 1) & 1);                                     // (that buffer was last read in tile t - 1)
+        __syncthreads();
+    }
+    // the other half-wave saw the other codes of every sub-tile
+    const float ob = __shfl_xor(best, 32);
+    const int oi = __shfl_xor(bidx, 32);
+    if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
+    if (half == 0 && row < rows) idx_out[((row / P) * num + g) * (long long)P + row % P] = bidx;
+}
+
+template <int DG>
+__global__ __launch_bounds__(vqg_threads<DG>()) void lvt_vq_nearest_gen_f32_kernel(
+    const float *__restrict__ z, long long rows, int ldz, int KC, const float *__restrict__ codebooks,
+    const float *__restrict__ nrm_g, long long *__restrict__ idx_out, int P, int num) {
+    using T = VqgF32<DG>;
+    constexpr int VQG_THREADS = vqg_threads<DG>();
+    constexpr int KT = T::KT, LDC = T::LDC, BUF = T::BUF, HD = DG / 2;
+    constexpr int CPR = DG / 4;                                                       // float4 chunks per code row
+    constexpr int NCH = KT * CPR;
+    constexpr int CH = (NCH + VQG_THREADS - 1) / VQG_THREADS;
+    static_assert(KT >= 32 && KT <= VQG_THREADS, "code tile");
+    extern __shared__ __attribute__((aligned(16))) unsigned char vqg_raw[];
+    const int g = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l31 = lane & 31, half = lane >> 5;
+    const float *E = codebooks + (long long)g * KC * DG;
+    const float *NR = nrm_g + (long long)g * KC;
+    const int ntl = (KC + KT - 1) / KT;
+
+    float4 st[CH];
+    float hv = 0.f;
+    auto fetch = [&](int t) {
+        const int k0 = t * KT, nc = KC - k0 < KT ? KC - k0 : KT;
+#pragma unroll
+        for (int i = 0; i < CH; ++i) {
+            const int c = tid + i * VQG_THREADS, code = c / CPR, q = c % CPR;
+            if (c < NCH && code < nc) st[i] = *reinterpret_cast<const float4 *>(E + (long long)(k0 + code) * DG + 4 * q);
+        }
+        if (tid < nc) hv = -0.5f * NR[k0 + tid];
+    };
+    auto put = [&](int t, int b) {
+        const int nc = KC - t * KT < KT ? KC - t * KT : KT;
+        float *Es = reinterpret_cast<float *>(vqg_raw + b * BUF);
+#pragma unroll
+        for (int i = 0; i < CH; ++i) {
+            const int c = tid + i * VQG_THREADS, code = c / CPR, q = c % CPR;
+            if (c < NCH && code < nc) {
+                Es[(4 * q + 0) * LDC + code] = st[i].x;
+                Es[(4 * q + 1) * LDC + code] = st[i].y;
+                Es[(4 * q + 2) * LDC + code] = st[i].z;
+                Es[(4 * q + 3) * LDC + code] = st[i].w;
+            }
+        }
+        if (tid < nc) Es[DG * LDC + tid] = hv;
+    };
+    fetch(0);
+
+    // the wave's row tile: lane holds dims HD half .. + HD - 1 of row tile * 32 + l31 (MFMA k slot = half)
+    const long long tile = (long long)blockIdx.x * (VQG_THREADS / 64) + wave;
+    float a[HD];
+    {
+        const long long row = tile * 32 + l31;
+        const float *zp = z + (row < rows ? row : rows - 1) * (long long)ldz + (long long)g * DG + HD * half;
+#pragma unroll
+        for (int q = 0; q < HD / 4; ++q) {
+            const float4 v = *reinterpret_cast<const float4 *>(zp + 4 * q);
+            a[4 * q] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
+        }
+    }
+    put(0, 0);
+    __syncthreads();
+
+    float best[16];
+    int bidx[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { best[r] = -INFINITY; bidx[r] = 0; }
+    for (int t = 0; t < ntl; ++t) {
+        if (t + 1 < ntl) fetch(t + 1);
+        const float *Es = reinterpret_cast<const float *>(vqg_raw + (t & 1) * BUF);
+        const float *Erd = Es + (HD * half) * LDC + l31;
+        const int nst = (KC - t * KT < KT ? KC - t * KT : KT) / 32;
+        for (int ct = 0; ct < nst; ++ct) {
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+            for (int j = 0; j < HD; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j], Erd[j * LDC + ct * 32], acc, 0, 0, 0);
+            // the lane's column is code ct * 32 + l31 of the tile: ascending per lane across sub-tiles and tiles
+            const float h = Es[DG * LDC + ct * 32 + l31];
+            const int code = t * KT + ct * 32 + l31;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float sc = acc[r] + h;
+                if (sc > best[r]) { best[r] = sc; bidx[r] = code; }
+            }
+        }
+        if (t + 1 < ntl) put(t + 1, (t + 1) & 1);
+        __syncthreads();
+    }
+    // reduce over the 32 lanes (code columns) of each half; equal scores -> lowest code
+#pragma unroll
+    for (int off = 16; off >= 1; off >>= 1) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float ob = __shfl_xor(best[r], off);
+            const int oi = __shfl_xor(bidx[r], off);
+            if (ob > best[r] || (ob == best[r] && oi < bidx[r])) { best[r] = ob; bidx[r] = oi; }
+        }
+    }
+    if (l31 == 0) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const long long rr = tile * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            if (rr < rows) idx_out[((rr / P) * num + g) * (long long)P + rr % P] = bidx[r];
+        }
+    }
+}
+
+// out[row][g*D + d] = E[g][idx][d] for any D % 4 == 0: D / 4 lanes move one (row, g) slice as float4, every lane keeps
+// GATHER_UNROLL independent index -> codebook -> store chains in flight (as lvt_vq_gather_kernel)
+__global__ __launch_bounds__(256) void lvt_vq_gather_gen_kernel(const long long *__restrict__ idx,
+                                                                const float *__restrict__ codebooks, long long rows, int num,
+                                                                int D, int KC, int P, float *__restrict__ out, int ldo) {
+    const int Q = D / 4;
+    const long long items = rows * num * Q;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long it = (long long)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride * GATHER_UNROLL) {
+        long long k[GATHER_UNROLL], row[GATHER_UNROLL]; int g[GATHER_UNROLL], q[GATHER_UNROLL];
+#pragma unroll
+        for (int u = 0; u < GATHER_UNROLL; ++u) {
+            const long long iu = it + stride * u, pr = iu / Q;
+            q[u] = (int)(iu - pr * Q); row[u] = pr / num; g[u] = (int)(pr - row[u] * num);
+            k[u] = iu < items ? idx[((row[u] / P) * num + g[u]) * (long long)P + row[u] % P] : 0;
+        }
+        float4 v[GATHER_UNROLL];
+#pragma unroll
+        for (int u = 0; u < GATHER_UNROLL; ++u)
+            v[u] = *reinterpret_cast<const float4 *>(codebooks + ((long long)g[u] * KC + k[u]) * D + q[u] * 4);
+#pragma unroll
+        for (int u = 0; u < GATHER_UNROLL; ++u)
+            if (it + stride * u < items) *reinterpret_cast<float4 *>(out + row[u] * ldo + (long long)g[u] * D + q[u] * 4) = v[u];
+    }
+}
+
+// EMA statistics of code range [k0, k0 + Kt) of group g over one row chunk (see the comment at the top of this section)
+#define EMAG_ROWS 64
+#define EMAG_ACC_BYTES 73728
+#define EMAG_MAXCH 8                        // staged float4 per thread: 64 rows x D / 4 <= 4096 at D = 256
+__global__ __launch_bounds__(EMA_THREADS) void lvt_vq_ema_partial_gen_kernel(
+    const long long *__restrict__ idx, const float *__restrict__ z, long long rows, int ldz, int num, int D, int KC, int P,
+    int Kt, long long rows_per_chunk, int nchunks, float *__restrict__ partial) {
+    extern __shared__ __attribute__((aligned(16))) float acc[];      // [Kt][D + 1], then the staging tile [64][D]
+    const int LD = D + 1, Q = D / 4;
+    float *tile = acc + ((Kt * LD + 3) & ~3);
+    const int g = blockIdx.y, c = blockIdx.x % nchunks, k0 = (blockIdx.x / nchunks) * Kt;
+    const int kn = KC - k0 < Kt ? KC - k0 : Kt;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int i = tid; i < kn * LD; i += EMA_THREADS) acc[i] = 0.f;
+    const long long r0 = (long long)c * rows_per_chunk;
+    const long long r1 = min(rows, r0 + rows_per_chunk);
+    auto code_of = [&](long long r) -> int {                        // code - k0 inside the range, else -1
+        if (r >= r1) return -1;
+        const long long k = idx[((r / P) * num + g) * (long long)P + r % P];
+        return k >= k0 && k < k0 + kn ? (int)(k - k0) : -1;
+    };
+    // only the rows of this range are fetched (the others stay zero in the tile and are never read)
+    float4 pre[EMAG_MAXCH];
+    auto fetch = [&](long long base) {
+#pragma unroll
+        for (int u = 0; u < EMAG_MAXCH; ++u) {
+            const int e = tid + u * EMA_THREADS;
+            pre[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (e < EMAG_ROWS * Q) {
+                const int rr = e / Q, q = e % Q;
+                if (code_of(base + rr) >= 0)
+                    pre[u] = *reinterpret_cast<const float4 *>(z + (base + rr) * (long long)ldz + (long long)g * D + 4 * q);
+            }
+        }
+    };
+    if (r0 < r1) fetch(r0);
+    __syncthreads();
+    for (long long base = r0; base < r1; base += EMAG_ROWS) {
+#pragma unroll
+        for (int u = 0; u < EMAG_MAXCH; ++u) {
+            const int e = tid + u * EMA_THREADS;
+            if (e < EMAG_ROWS * Q) *reinterpret_cast<float4 *>(&tile[(e / Q) * D + 4 * (e % Q)]) = pre[u];
+        }
+        const int code = code_of(base + lane);
+        __syncthreads();
+        if (base + EMAG_ROWS < r1) fetch(base + EMAG_ROWS);
+        // as lvt_vq_ema_partial_kernel: the rows of a code are summed in row order by the wave that owns the code's first row
+        unsigned long long todo = __ballot(code >= 0);
+        while (todo) {
+            const int j = __ffsll((long long)todo) - 1;
+            const int cj = __shfl(code, j);
+            const unsigned long long same = __ballot(code == cj);
+            todo &= ~same;
+            if ((j & 7) != wave) continue;
+            for (int d = lane; d < D; d += 64) {
+                float sum = 0.f;
+                unsigned long long mm = same;
+                while (mm) { const int r_ = __ffsll((long long)mm) - 1; mm &= mm - 1; sum += tile[r_ * D + d]; }
+                acc[cj * LD + d] += sum;
+            }
+            if (lane == 0) acc[cj * LD + D] += (float)__popcll(same);
+        }
+        __syncthreads();
+    }
+    __syncthreads();
+    float *dst = partial + ((long long)g * nchunks + c) * ((long long)KC * LD) + (long long)k0 * LD;
+    for (int i = tid; i < kn * LD; i += EMA_THREADS) dst[i] = acc[i];
+}
+
+// lvt_vq_ema_finalize_kernel for a runtime D
+__global__ __launch_bounds__(512) void lvt_vq_ema_finalize_gen_kernel(const float *__restrict__ stats, int KC, int D,
+                                                                      float decay, float one_minus_decay, float eps,
+                                                                      float *__restrict__ running_size,
+                                                                      float *__restrict__ running_sum,
+                                                                      float *__restrict__ weight) {
+    __shared__ float red[512];
+    __shared__ float ntot;
+    const int g = blockIdx.x, tid = threadIdx.x;
+    float *rs = running_size + (long long)g * KC;
+    float *rsum = running_sum + (long long)g * KC * D;
+    float *w = weight + (long long)g * KC * D;
+    const float *st = stats + (long long)g * KC * (D + 1);
+    float part = 0.f;
+    for (int k = tid; k < KC; k += blockDim.x) {
+        const float v = rs[k] * decay + one_minus_decay * st[k * (D + 1) + D];
+        rs[k] = v;
+        part += v;
+    }
+    red[tid] = part;
+    __syncthreads();
+    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) ntot = red[0];
+    __syncthreads();
+    const float n = ntot;
+    constexpr int FB = 8;
+    const int tot = KC * D;
+    for (int i0 = tid; i0 < tot; i0 += blockDim.x * FB) {
+        float a[FB], b[FB], c[FB];
+#pragma unroll
+        for (int u = 0; u < FB; ++u) {
+            const int i = i0 + u * blockDim.x;
+            const bool ok = i < tot;
+            const int k = ok ? i / D : 0, d = ok ? i % D : 0;
+            a[u] = ok ? rsum[i] : 0.f; b[u] = st[k * (D + 1) + d]; c[u] = rs[k];
+        }
+#pragma unroll
+        for (int u = 0; u < FB; ++u) {
+            const int i = i0 + u * blockDim.x;
+            if (i < tot) {
+                const float s = a[u] * decay + one_minus_decay * b[u];
+                rsum[i] = s;
+                const float size_ = (c[u] + eps) / (n + KC * eps) * n;
+                w[i] = s / size_;
+            }
+        }
+    }
+}
+
+// ---- host side of the generic geometry ----------------------------------------------------------------------------------
+static bool vq_instantiated(int D, int KC) { return D == VQ_D && (KC == 512 || KC == 256 || KC == 128); }
+static bool vq_generic_search_ok(int D, int KC) { return D % 16 == 0 && D >= 16 && D <= 256 && KC % 64 == 0 && KC >= 64 && KC <= 2048; }
+
+// workspace of the generic search: nrm, emax, hcb [num][KC] fp32, gsc [num][2], hi, lo [num][KC][D] fp16 (256-byte aligned pieces)
+static size_t vqg_al(size_t b) { return (b + 255) & ~(size_t)255; }
+struct VqgWs { float *nrm, *emax, *hcb, *gsc; unsigned short *hi, *lo; size_t bytes; };
+static VqgWs vqg_ws(void *base, int num, int D, int KC) {
+    VqgWs w;
+    char *p = (char *)base;
+    const size_t f = vqg_al((size_t)num * KC * 4), gs = vqg_al((size_t)num * 8), h = vqg_al((size_t)num * KC * D * 2);
+    w.nrm = (float *)p; w.emax = (float *)(p + f); w.hcb = (float *)(p + 2 * f); w.gsc = (float *)(p + 3 * f);
+    w.hi = (unsigned short *)(p + 3 * f + gs); w.lo = (unsigned short *)(p + 3 * f + gs + h);
+    w.bytes = 3 * f + gs + 2 * h;
+    return w;
+}
+
+template <int DG>
+static int vqg_search(const float *z, long long rows, int ldz, int num, int KC, const float *codebooks, long long *idx_out,
+                      int P, bool f32, const VqgWs &w, hipStream_t s) {
+    constexpr int VQG_THREADS = vqg_threads<DG>();
+    const dim3 grid((unsigned)lvt_cdiv(rows, 32 * (VQG_THREADS / 64)), num);
+    hipError_t e;
+    if (f32) {
+        const int smem = 2 * VqgF32<DG>::BUF;
+        e = hipFuncSetAttribute((const void *)lvt_vq_nearest_gen_f32_kernel<DG>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        if (e != hipSuccess) { lvt_set_error("vq_nearest: cannot get %d B LDS: %s", smem, hipGetErrorString(e)); return LVT_ELAUNCH; }
+        hipLaunchKernelGGL(lvt_vq_nearest_gen_f32_kernel<DG>, grid, dim3(VQG_THREADS), smem, s, z, rows, ldz, KC, codebooks,
+                           (const float *)w.nrm, idx_out, P, num);
+        LVT_CHECK_LAUNCH("lvt_vq_nearest_gen_f32_kernel");
+    } else {
+        const int smem = 2 * VqgF16<DG>::BUF;
+        e = hipFuncSetAttribute((const void *)lvt_vq_nearest_gen_f16x2_kernel<DG>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        if (e != hipSuccess) { lvt_set_error("vq_nearest: cannot get %d B LDS: %s", smem, hipGetErrorString(e)); return LVT_ELAUNCH; }
+        hipLaunchKernelGGL(lvt_vq_nearest_gen_f16x2_kernel<DG>, grid, dim3(VQG_THREADS), smem, s, z, rows, ldz, KC,
+                           (const unsigned short *)w.hi, (const unsigned short *)w.lo, (const float *)w.hcb,
+                           (const float *)w.gsc, idx_out, P, num);
+        LVT_CHECK_LAUNCH("lvt_vq_nearest_gen_f16x2_kernel");
+    }
+    return LVT_OK;
+}
+
+static int vq_nearest_generic(const float *z, long long rows, int ldz, int num, int D, int KC, const float *codebooks,
+                              long long *idx_out, int P, int flags, void *workspace, size_t workspace_bytes, hipStream_t s) {
+    LVT_REQUIRE(vq_generic_search_ok(D, KC),
+                "vq_nearest: unsupported geometry D=%d KC=%d (D: multiple of 16 in 16..256; KC: multiple of 64 in 64..2048)", D, KC);
+    LVT_REQUIRE(rows > 0 && num > 0 && P > 0 && rows % P == 0, "vq_nearest: bad rows/P");
+    LVT_REQUIRE(ldz % 4 == 0 && ldz >= num * D && lvt_aligned16(z) && lvt_aligned16(codebooks), "vq_nearest: alignment / ldz");
+    const VqgWs w = vqg_ws(workspace, num, D, KC);
+    if (!workspace || workspace_bytes < w.bytes || ((uintptr_t)workspace & 255)) {
+        lvt_set_error("vq_nearest: the generic search needs a 256-byte aligned workspace of %zu B", w.bytes);
+        return LVT_EWORKSPACE;
+    }
+    // bf16x3 (neither math flag) takes the exact f32 form here
+    const bool f32 = (flags & LVT_MATH_F32) || !(flags & LVT_MATH_F16X2);
+    hipLaunchKernelGGL(lvt_vq_gen_norms_kernel, dim3((unsigned)lvt_cdiv(KC, 256), num), dim3(256), 0, s, codebooks, KC, D,
+                       w.nrm, w.emax);
+    LVT_CHECK_LAUNCH("lvt_vq_gen_norms_kernel");
+    if (!f32) {
+        const long long nq = (long long)KC * D / 4;
+        const unsigned nb = (unsigned)(lvt_cdiv(nq, 256 * 4) < 64 ? lvt_cdiv(nq, 256 * 4) : 64);
+        hipLaunchKernelGGL(lvt_vq_gen_planes_kernel, dim3(nb, num), dim3(256), 0, s, codebooks, KC, D, (const float *)w.nrm,
+                           (const float *)w.emax, w.hi, w.lo, w.hcb, w.gsc);
+        LVT_CHECK_LAUNCH("lvt_vq_gen_planes_kernel");
+    }
+    switch (D) {
+#define VQG_CASE(DV) case DV: return vqg_search<DV>(z, rows, ldz, num, KC, codebooks, idx_out, P, f32, w, s);
+        VQG_CASE(16) VQG_CASE(32) VQG_CASE(48) VQG_CASE(64) VQG_CASE(80) VQG_CASE(96) VQG_CASE(112) VQG_CASE(128)
+        VQG_CASE(144) VQG_CASE(160) VQG_CASE(176) VQG_CASE(192) VQG_CASE(208) VQG_CASE(224) VQG_CASE(240) VQG_CASE(256)
+#undef VQG_CASE
+    }
+    lvt_set_error("vq_nearest: D=%d", D);
+    return LVT_EINVAL;
+}
+
+// generic EMA statistics: codes per range and row chunks (~two workgroups per CU over all groups and ranges)
+static void emag_plan(long long rows, int num, int D, int KC, int *kt, long long *rows_per_chunk, int *nchunks) {
+    int k = EMAG_ACC_BYTES / (4 * (D + 1)) / 64 * 64;
+    if (k > KC) k = KC;
+    const int nr = (KC + k - 1) / k;
+    long long target = 2LL * LVT_NUM_CU / ((long long)(num > 0 ? num : 1) * nr);
+    if (target < 1) target = 1;
+    long long rpc = lvt_cdiv(rows, target);
+    rpc = lvt_cdiv(rpc, 64) * 64;
+    if (rpc < 256) rpc = 256;
+    *kt = k;
+    *rows_per_chunk = rpc;
+    *nchunks = (int)lvt_cdiv(rows, rpc);
+}
+
 // ------------------------------------------------------------------------------------------------
 static int vq_smem_bytes(int KC) { return (VQ_D * (KC + 1) + KC) * (int)sizeof(float); }
 
@@ -946,10 +1518,17 @@ extern "C" size_t lvt_vq_nearest_workspace_bytes(long long rows, int num, int KC
     return (size_t)rows * num * nparts * (sizeof(float) + sizeof(int));
 }
 
+extern "C" size_t lvt_vq_nearest_generic_workspace_bytes(int num, int D, int KC) {
+    return vqg_ws(nullptr, num, D, KC).bytes;
+}
+
 extern "C" int lvt_vq_nearest(const float *z, long long rows, int ldz, int num, int D, int KC,
                               const float *codebooks, long long *idx_out, int P, int flags, void *workspace,
                               size_t workspace_bytes, void *stream) {
     LVT_REQUIRE(z && codebooks && idx_out, "vq_nearest: null pointer");
+    if ((flags & LVT_VQ_GENERIC) || !vq_instantiated(D, KC))
+        return vq_nearest_generic(z, rows, ldz, num, D, KC, codebooks, idx_out, P, flags, workspace, workspace_bytes,
+                                  (hipStream_t)stream);
     LVT_REQUIRE(D == VQ_D, "vq_nearest: only D=%d per codebook is instantiated (got %d)", VQ_D, D);
     LVT_REQUIRE(KC == 512 || KC == 256 || KC == 128, "vq_nearest: codebook size %d not instantiated", KC);
     LVT_REQUIRE(rows > 0 && num > 0 && P > 0 && rows % P == 0, "vq_nearest: bad rows/P");
@@ -1025,6 +1604,17 @@ extern "C" int lvt_vq_nearest(const float *z, long long rows, int ldz, int num, 
 
 extern "C" int lvt_vq_gather(const long long *idx, const float *codebooks, long long rows, int num, int D, int KC,
                              int P, float *out, int ldo, void *stream) {
+    if (D != VQ_D) {
+        LVT_REQUIRE(idx && codebooks && out && D % 4 == 0 && D > 0 && num > 0 && rows > 0 && P > 0 && rows % P == 0 &&
+                    ldo >= num * D, "vq_gather: bad args");
+        LVT_REQUIRE(ldo % 4 == 0 && lvt_aligned16(out) && lvt_aligned16(codebooks), "vq_gather: out / codebooks must be 16-byte aligned");
+        const long long items = rows * num * (D / 4);
+        const int blocks = (int)(lvt_cdiv(items, 256 * GATHER_UNROLL) < 8192 ? lvt_cdiv(items, 256 * GATHER_UNROLL) : 8192);
+        hipLaunchKernelGGL(lvt_vq_gather_gen_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, idx, codebooks, rows,
+                           num, D, KC, P, out, ldo);
+        LVT_CHECK_LAUNCH("lvt_vq_gather_gen_kernel");
+        return LVT_OK;
+    }
     LVT_REQUIRE(idx && codebooks && out && D == VQ_D && rows > 0 && rows % P == 0, "vq_gather: bad args");
     const long long pairs = rows * num;
     LVT_REQUIRE(ldo % 4 == 0 && lvt_aligned16(out) && lvt_aligned16(codebooks), "vq_gather: out / codebooks must be 16-byte aligned");
@@ -1046,12 +1636,42 @@ static void ema_chunks(long long rows, int num, long long *rows_per_chunk, int *
 }
 extern "C" size_t lvt_vq_ema_workspace_bytes(long long rows, int num, int D, int KC) {
     long long rpc; int nch;
+    if (!vq_instantiated(D, KC)) {
+        int kt;
+        emag_plan(rows, num, D, KC, &kt, &rpc, &nch);
+        return (size_t)num * nch * KC * (D + 1) * sizeof(float);
+    }
     ema_chunks(rows, num, &rpc, &nch);
     return (size_t)num * nch * KC * (D + 1) * sizeof(float);
 }
 extern "C" int lvt_vq_ema_accumulate(const long long *idx, const float *z, long long rows, int ldz, int num, int D,
                                      int KC, int P, float *stats, void *workspace, size_t workspace_bytes,
                                      void *stream) {
+    if (!vq_instantiated(D, KC)) {
+        LVT_REQUIRE(idx && z && stats && rows > 0 && num > 0 && P > 0 && rows % P == 0, "vq_ema_accumulate: bad args");
+        LVT_REQUIRE(D % 4 == 0 && D >= 4 && D <= 256 && KC >= 1 && KC <= 2048,
+                    "vq_ema_accumulate: unsupported geometry D=%d KC=%d (D: multiple of 4 up to 256; KC <= 2048)", D, KC);
+        LVT_REQUIRE(ldz % 4 == 0 && ldz >= num * D && lvt_aligned16(z), "vq_ema_accumulate: alignment / ldz");
+        int kt; long long rpc; int nch;
+        emag_plan(rows, num, D, KC, &kt, &rpc, &nch);
+        if (!workspace || workspace_bytes < lvt_vq_ema_workspace_bytes(rows, num, D, KC)) {
+            lvt_set_error("vq_ema_accumulate: workspace too small");
+            return LVT_EWORKSPACE;
+        }
+        hipStream_t s = (hipStream_t)stream;
+        const int smem = (((kt * (D + 1) + 3) & ~3) + EMAG_ROWS * D) * (int)sizeof(float);
+        const hipError_t e = hipFuncSetAttribute((const void *)lvt_vq_ema_partial_gen_kernel,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        if (e != hipSuccess) { lvt_set_error("vq_ema_accumulate: cannot get %d B LDS: %s", smem, hipGetErrorString(e)); return LVT_ELAUNCH; }
+        hipLaunchKernelGGL(lvt_vq_ema_partial_gen_kernel, dim3(nch * ((KC + kt - 1) / kt), num), dim3(EMA_THREADS), smem, s, idx,
+                           z, rows, ldz, num, D, KC, P, kt, rpc, nch, (float *)workspace);
+        LVT_CHECK_LAUNCH("lvt_vq_ema_partial_gen_kernel");
+        const long long per_group = (long long)KC * (D + 1);
+        hipLaunchKernelGGL(lvt_vq_ema_reduce_kernel, dim3((unsigned)lvt_cdiv(per_group, 256), num), dim3(256), 0, s,
+                           (const float *)workspace, nch, per_group, stats);
+        LVT_CHECK_LAUNCH("lvt_vq_ema_reduce_kernel");
+        return LVT_OK;
+    }
     LVT_REQUIRE(idx && z && stats && D == VQ_D && rows > 0 && rows % P == 0, "vq_ema_accumulate: bad args");
     LVT_REQUIRE(KC == 512 || KC == 256 || KC == 128, "vq_ema_accumulate: codebook size %d not instantiated", KC);
     long long rpc; int nch;
@@ -1082,9 +1702,16 @@ extern "C" int lvt_vq_ema_accumulate(const long long *idx, const float *z, long 
 
 extern "C" int lvt_vq_ema_finalize(const float *stats, int num, int D, int KC, float decay, float eps,
                                    float *running_size, float *running_sum, float *weight, void *stream) {
-    LVT_REQUIRE(stats && running_size && running_sum && weight && D == VQ_D, "vq_ema_finalize: bad args");
+    LVT_REQUIRE(stats && running_size && running_sum && weight && num > 0, "vq_ema_finalize: bad args");
     // the reference evaluates (1 - decay) in double precision python and hands it to add_(alpha=...)
     const float omd = (float)(1.0 - (double)decay);
+    if (D != VQ_D) {
+        LVT_REQUIRE(D > 0 && D <= 256 && KC > 0 && KC <= 2048, "vq_ema_finalize: unsupported geometry D=%d KC=%d", D, KC);
+        hipLaunchKernelGGL(lvt_vq_ema_finalize_gen_kernel, dim3(num), dim3(512), 0, (hipStream_t)stream, stats, KC, D, decay,
+                           omd, eps, running_size, running_sum, weight);
+        LVT_CHECK_LAUNCH("lvt_vq_ema_finalize_gen_kernel");
+        return LVT_OK;
+    }
     hipLaunchKernelGGL(lvt_vq_ema_finalize_kernel, dim3(num), dim3(512), 0, (hipStream_t)stream, stats, KC, decay,
                        omd, eps, running_size, running_sum, weight);
     LVT_CHECK_LAUNCH("lvt_vq_ema_finalize_kernel");

@@ -14,7 +14,7 @@ _LIB_PATH = os.environ.get("LVT_HIP_LIB") or os.path.join(os.path.dirname(_HERE)
 
 EPI_BIAS, EPI_RESIDUAL, EPI_RELU, EPI_TANH, EPI_MASK, EPI_ACCUM, EPI_PLANES = 1, 2, 4, 8, 16, 32, 64
 CAUSAL_KMAX, CAUSAL_KMIN, CAUSAL_TILE = 1 << 8, 1 << 9, 1 << 10      # causal attention products (include/lvt_hip.h)
-ABI_VERSION = 610           # lvt_version() of the library this module binds (argument lists below)
+ABI_VERSION = 620           # lvt_version() of the library this module binds (argument lists below)
 MATH_F32 = 1 << 16          # per-call arithmetic selectors of the engine entry points (include/lvt_hip.h)
 MATH_F16X2 = 1 << 18
 ONEHOT_DENSE = 1 << 19
@@ -144,6 +144,7 @@ def _declare(lib):
         "lvt_colsum_workspace_bytes": (sz, [cll, ci]),
         "lvt_colsum": (ci, [vp, cll, ci, cll, vp, vp, sz, vp]),
         "lvt_vq_nearest_workspace_bytes": (sz, [cll, ci, ci]),
+        "lvt_vq_nearest_generic_workspace_bytes": (sz, [ci, ci, ci]),
         "lvt_vq_nearest": (ci, [vp, cll, ci, ci, ci, ci, vp, vp, ci, ci, vp, sz, vp]),
         "lvt_vq_gather": (ci, [vp, vp, cll, ci, ci, ci, ci, vp, ci, vp]),
         "lvt_vq_ema_workspace_bytes": (sz, [cll, ci, ci, ci]),

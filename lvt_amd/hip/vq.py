@@ -7,20 +7,24 @@ from . import binding as L
 
 
 VQ_COARSE = 1 << 17          # include/lvt_hip.h: LVT_VQ_COARSE
+VQ_GENERIC = 1 << 22         # include/lvt_hip.h: LVT_VQ_GENERIC (tests / A-B only)
 _COARSE_DEFAULT = bool(os.environ.get("LVT_VQ_COARSE"))
 
 
-def nearest(z, codebooks, P, coarse=None):
+def nearest(z, codebooks, P, coarse=None, generic=False):
     """z (rows, ldz) channels-last, codebooks (num, K, D) -> idx int64 (rows/P, num, P).
-    coarse=True: the coarse-then-exact search (same exact argmin; opt-in, see csrc/vq.hip for when it pays)."""
+    coarse=True: the coarse-then-exact search (same exact argmin; opt-in, see csrc/vq.hip for when it pays).
+    generic=True: the generic-geometry search even where a specialised kernel exists (tests and A/B measurements; every
+    geometry other than D == 64, K in {128, 256, 512} takes it anyway)."""
     L.require(z, codebooks)
     rows, ldz = z.shape
     num, K, D = codebooks.shape
     idx = torch.empty(rows // P, num, P, dtype=torch.int64, device=z.device)
     lib = L.lib()
-    nws = lib.lvt_vq_nearest_workspace_bytes(rows, num, K)
+    nws = max(lib.lvt_vq_nearest_workspace_bytes(rows, num, K), lib.lvt_vq_nearest_generic_workspace_bytes(num, D, K))
     ws = L.workspace(nws, z.device, "vq_nearest")
-    L.check(lib.lvt_vq_nearest(L.ptr(z), rows, ldz, num, D, K, L.ptr(codebooks), L.ptr(idx), P, L.math_flag() | (VQ_COARSE if (coarse if coarse is not None else _COARSE_DEFAULT) else 0),
+    flags = L.math_flag() | (VQ_COARSE if (coarse if coarse is not None else _COARSE_DEFAULT) else 0) | (VQ_GENERIC if generic else 0)
+    L.check(lib.lvt_vq_nearest(L.ptr(z), rows, ldz, num, D, K, L.ptr(codebooks), L.ptr(idx), P, flags,
                                L.ptr(ws), nws, L.stream_ptr()), "lvt_vq_nearest")
     return idx
 

@@ -23,6 +23,29 @@ from ...hip import ew, vq
 from ...layers.all_reduce import all_reduce_sum_async_
 from .. import convstack
 
+SUPPORTED_GEOMETRY = ("sub-vector width DIM / NUM: a multiple of 16 from 16 to 256 (product quantiser, DVQEmbedding) or "
+                      "DIM a multiple of 64 (one wide codebook, SingleVQEmbedding); codebook size SIZE: a multiple of 64 "
+                      "from 64 to 2048")
+
+
+def check_geometry(num, K, D, single=False):
+    """Raise NotImplementedError unless (NUM, SIZE, DIM) is a geometry the HIP quantiser kernels support (csrc/vq.hip).
+    single=True: SingleVQEmbedding, which searches the whole DIM-wide codebook and gathers / updates it as DIM / 64 groups of
+    64 dims; otherwise the product quantiser, whose kernels see sub-vectors of DIM / NUM dims (also when NUM == 1)."""
+    if num < 1 or D % num:
+        raise NotImplementedError("CODEBOOK.DIM (%d) must be a multiple of CODEBOOK.NUM (%d); supported: %s"
+                                  % (D, num, SUPPORTED_GEOMETRY))
+    dg = D // num
+    if single:
+        ok_d = D % 64 == 0 and D > 0
+    else:
+        ok_d = dg % 16 == 0 and 16 <= dg <= 256
+    if not ok_d:
+        raise NotImplementedError("unsupported codebook geometry NUM=%d DIM=%d (sub-vector width %d); supported: %s"
+                                  % (num, D, dg, SUPPORTED_GEOMETRY))
+    if K % 64 or not 64 <= K <= 2048:
+        raise NotImplementedError("unsupported codebook SIZE=%d; supported: %s" % (K, SUPPORTED_GEOMETRY))
+
 
 class VQEmbedding(nn.Module):
     """One codebook: parameter / buffer container (vq_embedding.py:9-21)."""
@@ -129,9 +152,8 @@ class SingleVQEmbedding(VQEmbedding):
     (vq_embedding.py:48-59) to every group with the same counts."""
 
     def __init__(self, K, D, ema):
+        check_geometry(1, K, D, single=True)
         super().__init__(K, D, ema)
-        if D % 64:
-            raise NotImplementedError("the HIP quantiser works on 64-d groups: CODEBOOK.DIM must be a multiple of 64 (got %d)" % D)
         self.num, self.groups = 1, D // 64
         self._pending = None
 
@@ -219,9 +241,7 @@ class SingleVQEmbedding(VQEmbedding):
 class DVQEmbedding(nn.Module):
     def __init__(self, num, K, D, ema):
         super().__init__()
-        assert D % num == 0
-        if D // num != 64:
-            raise NotImplementedError("the HIP quantiser is instantiated for 64-d sub-vectors (got %d)" % (D // num))
+        check_geometry(num, K, D)
         self.num, self.D, self.K, self.ema = num, D, K, ema
         self.decay, self.eps = 0.99, 1e-5
         self.ve = nn.ModuleList([VQEmbedding(K, D // num, ema) for _ in range(num)])
