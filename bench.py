@@ -11,7 +11,10 @@ two PR-DVQVAE2 train steps (fwd + bwd + Adam) of 32 clips x 16 frames each (BASE
 one DSFVT train step (fwd + bwd + RMSprop) on 64 slices, one random subscale slice per clip (configs[2]/[3]:
 IMS_PER_BATCH 64).  `value` = 64 * N * K / (time of exactly K such steps between two barriers, max over ranks).
 One process per GPU, gradients averaged by a bucketed RCCL all-reduce overlapped with backward, EMA statistics by
-one fused all-reduce; weak scaling.  Rank 0 prints ONE JSON line.  Besides the contract keys it carries
+one fused all-reduce; weak scaling.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the line: the contract keys,
+`step_ms` and the configuration.  With --full it goes on after the timed region and the line also carries
   roofline      the matrix-core engine launches of the step (conv / GEMM / fused attention kernels), event-timed per
                 launch on the launch stream in a SECOND pass of the same K steps (a timing event is a barrier packet;
                 inside the timed region it costs ~15 % of a step)
@@ -93,16 +96,19 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--dp-single-rank", action="store_true",
                     help="with --gpus 1: join a ONE-rank RCCL group and keep the gradient reducers active (all-reduces are "
-                         "identities there), so that `comm` reports the exposed communication of the data-parallel path")
+                         "identities there), so that `comm` (--full) reports the exposed communication of the data-parallel path")
     ap.add_argument("--rccl-channels", type=int, default=0,
                     help="cap RCCL's channels (NCCL_MIN_NCHANNELS = NCCL_MAX_NCHANNELS = n, set before the process group is made): "
                          "every channel of an all-reduce is a workgroup that needs a CU while the backward pass runs one engine "
-                         "workgroup per CU; 0 = RCCL's default.  Reported under comm.rccl_channels")
+                         "workgroup per CU; 0 = RCCL's default.  Reported under comm.rccl_channels (--full)")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batches", type=int, default=4, help="distinct synthetic batches rotated through the steps")
     ap.add_argument("--batch-clips", type=int, default=32, help="clips per GPU per VQ-VAE train step (BASELINE: 32)")
     ap.add_argument("--dsfvt-batch", type=int, default=64, help="slices (= clips) per GPU per DSFVT train step (BASELINE: 64)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure and check everything else the line can carry (roofline, comm, "
+                         "parity, extra, cpu_baseline); the --no-* options below drop parts of it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-legs", action="store_true", help="skip the per-leg timed regions under `extra`")
     ap.add_argument("--no-strict-f32", action="store_true", help="skip the secondary LVT_MATH=f32 figures")
@@ -860,84 +866,86 @@ def run(args):
 
     # Pass 1 -- the timed region: exactly K steps, nothing but the product path between the two barriers.
     elapsed, stats, (losses, ds_loss) = timed_steps(step, args.steps, args.warmup, world, device)
-    # what the last timed step computed, before pass 2 trains the models further
+    # what the last timed step computed, before a --full run trains the models further
     dumped = dump_outputs(args.dump_outputs, losses, ds_loss, vq, ds) if args.dump_outputs and rank == 0 else None
-    # Pass 2 -- the same K steps again with a HIP event pair around every engine launch (on the launch stream).
-    timer, instrumented_ms = instrumented(step, args.steps, args.warmup + args.steps)
     math_mode = L.get_math_mode()
-    es = engine_summary(timer, args.steps, math_mode)
-
-    # communication: what RCCL sees, and what the step costs with the reducers switched off (gradients stay local)
-    reducers = list(getattr(vq.model, "_reducers", [])) + list(getattr(ds.model, "_reducers", []))
     grouped = world > 1 or single
-    if grouped:     # what RCCL itself reports after a collective of this process group has run
-        probe = torch.ones(1, device=device)
-        dist.all_reduce(probe)
-        torch.cuda.synchronize()
-    comm = {"world_size": dist.get_world_size() if grouped else 1, "backend": dist.get_backend() if grouped else None,
-            "ranks_seen_by_allreduce": int(probe.item()) if grouped else 1, "single_rank_group": single,
-            "allreduce_bytes_per_step": int(sum(r.bytes_per_backward for r in reducers if r in vq.model._reducers) * vq_per_step
-                                            + sum(r.bytes_per_backward for r in reducers if r in ds.model._reducers))
-            if reducers else 0,
-            "ema_allreduce_bytes_per_step": (4 * 512 * (64 + 1) * 4) * vq_per_step if world > 1 else 0,
-            # CU footprint of the collectives: each RCCL channel is a workgroup competing with the one-workgroup-per-CU engine
-            # launches of the backward pass; A/B it with --rccl-channels on the 8-GPU node (unmeasured here: one GPU per box)
-            "rccl_channels": {"requested": args.rccl_channels or None,
-                              "NCCL_MIN_NCHANNELS": os.environ.get("NCCL_MIN_NCHANNELS"),
-                              "NCCL_MAX_NCHANNELS": os.environ.get("NCCL_MAX_NCHANNELS")},
-            "bucket_order": ("arrival order measured in the first backward" if reducers and all(r._calibrated for r in reducers)
-                             else "reverse registration order") if reducers else None}
-    if grouped:
-        for r in reducers:
-            r.enabled = False
-        n3 = max(5, args.steps // 2)
-        e3, _, _ = timed_steps(step, n3, 0, world, device)
-        for r in reducers:
-            r.enabled = True
-        comm["ms_per_step_without_grad_allreduce"] = round(e3 / n3 * 1e3, 3)
-        comm["comm_exposed_ms_per_step"] = round(elapsed / args.steps * 1e3 - e3 / n3 * 1e3, 3)
-        comm["note"] = ("gradient buckets are all-reduced (ReduceOp.AVG) on a side stream as their last gradient arrives; "
-                        "`comm_exposed` = timed step - the same step with the reducers off (replicas then diverge: timing only)")
-
     extra = {}
-    if not args.no_legs:
-        nl = max(10, args.steps)
-        extra["vqvae"] = leg_alone("vqvae", vq, nl, 3, world, device, "clips", "r06_vqvae_pmc_hbm_traffic.json",
-                                   "lvt_conv_patch_kernel<0,1,2> / lvt_conv_wgrad_frames_kernel<0,1> (frame-resident 3x3 and "
-                                   "4x4/stride-2 layers) + lvt_gemm_kernel<*> (1x1 and image-side layers)",
-                                   not args.no_strict_f32)
-        extra["dsfvt"] = leg_alone("dsfvt", ds, max(10, args.steps // 2), 2, world, device, "samples",
-                                   "r06_dsfvt_pmc_hbm_traffic.json",
-                                   "lvt_gemm_wide_kernel<*> (QKV / proj / FFN products, their data and weight gradients; f16x2) + "
-                                   "lvt_attn_fwd_flash_kernel / lvt_attn_bwd_flash_a / _b (flash attention on fp32 operands, per-row f16x2)", not args.no_strict_f32)
-        extra["host_fed"] = host_fed(vq, ds, max(6, args.steps // 2), world, device)
-        v1, v2 = extra["vqvae"]["clips_per_s"], extra["dsfvt"]["samples_per_s"]
-        extra["legs_combined_harmonic"] = {"clips_per_s": round(1.0 / (1.0 / v1 + 1.0 / v2), 3),
-                                           "note": "1/(1/vqvae + 1/dsfvt) of the two legs timed alone: cross-check of `value`"}
-    # the same job with every product on the plain fp32 MFMA instruction (LVT_MATH=f32), from the two legs timed alone in that mode
     strict_f32 = None
-    if "vqvae" in extra and "strict_f32_mfma" in extra["vqvae"] and "strict_f32_mfma" in extra["dsfvt"]:
-        f1, f2 = extra["vqvae"]["strict_f32_mfma"]["clips_per_s"], extra["dsfvt"]["strict_f32_mfma"]["samples_per_s"]
-        strict_f32 = {"clips_per_s": round(1.0 / (1.0 / f1 + 1.0 / f2), 3), "ratio_to_value": None,
-                      "note": "LVT_MATH=f32 (v_mfma_f32_32x32x2_f32 everywhere): 1/(1/vqvae + 1/dsfvt) of the two legs timed alone "
-                              "in that mode (extra.*.strict_f32_mfma); `value` is measured in `math_mode`"}
-    gate_state = None
     parity = None
-    if not args.no_parity and rank == 0:
-        parity, vq_enc, gate_state = vq_gates(vq, device, 8)
-        extra["vq_encode"] = vq_enc
-        parity["dsfvt_loss"] = round(float(ds_loss.detach()), 6)
-        parity["vqvae_loss"] = {k: round(float(v.detach()), 6) for k, v in losses.items()}
+    gate_state = None
+    if args.full:
+        # Pass 2 -- the same K steps again with a HIP event pair around every engine launch (on the launch stream).
+        timer, instrumented_ms = instrumented(step, args.steps, args.warmup + args.steps)
+        es = engine_summary(timer, args.steps, math_mode)
+
+        # communication: what RCCL sees, and what the step costs with the reducers switched off (gradients stay local)
+        reducers = list(getattr(vq.model, "_reducers", [])) + list(getattr(ds.model, "_reducers", []))
+        if grouped:     # what RCCL itself reports after a collective of this process group has run
+            probe = torch.ones(1, device=device)
+            dist.all_reduce(probe)
+            torch.cuda.synchronize()
+        comm = {"world_size": dist.get_world_size() if grouped else 1, "backend": dist.get_backend() if grouped else None,
+                "ranks_seen_by_allreduce": int(probe.item()) if grouped else 1, "single_rank_group": single,
+                "allreduce_bytes_per_step": int(sum(r.bytes_per_backward for r in reducers if r in vq.model._reducers) * vq_per_step
+                                                + sum(r.bytes_per_backward for r in reducers if r in ds.model._reducers))
+                if reducers else 0,
+                "ema_allreduce_bytes_per_step": (4 * 512 * (64 + 1) * 4) * vq_per_step if world > 1 else 0,
+                # CU footprint of the collectives: each RCCL channel is a workgroup competing with the one-workgroup-per-CU engine
+                # launches of the backward pass; A/B it with --rccl-channels on an 8-GPU node (not measured yet)
+                "rccl_channels": {"requested": args.rccl_channels or None,
+                                  "NCCL_MIN_NCHANNELS": os.environ.get("NCCL_MIN_NCHANNELS"),
+                                  "NCCL_MAX_NCHANNELS": os.environ.get("NCCL_MAX_NCHANNELS")},
+                "bucket_order": ("arrival order measured in the first backward" if reducers and all(r._calibrated for r in reducers)
+                                 else "reverse registration order") if reducers else None}
+        if grouped:
+            for r in reducers:
+                r.enabled = False
+            n3 = max(5, args.steps // 2)
+            e3, _, _ = timed_steps(step, n3, 0, world, device)
+            for r in reducers:
+                r.enabled = True
+            comm["ms_per_step_without_grad_allreduce"] = round(e3 / n3 * 1e3, 3)
+            comm["comm_exposed_ms_per_step"] = round(elapsed / args.steps * 1e3 - e3 / n3 * 1e3, 3)
+            comm["note"] = ("gradient buckets are all-reduced (ReduceOp.AVG) on a side stream as their last gradient arrives; "
+                            "`comm_exposed` = timed step - the same step with the reducers off (replicas then diverge: timing only)")
+
+        if not args.no_legs:
+            nl = max(10, args.steps)
+            extra["vqvae"] = leg_alone("vqvae", vq, nl, 3, world, device, "clips", "r06_vqvae_pmc_hbm_traffic.json",
+                                       "lvt_conv_patch_kernel<0,1,2> / lvt_conv_wgrad_frames_kernel<0,1> (frame-resident 3x3 and "
+                                       "4x4/stride-2 layers) + lvt_gemm_kernel<*> (1x1 and image-side layers)",
+                                       not args.no_strict_f32)
+            extra["dsfvt"] = leg_alone("dsfvt", ds, max(10, args.steps // 2), 2, world, device, "samples",
+                                       "r06_dsfvt_pmc_hbm_traffic.json",
+                                       "lvt_gemm_wide_kernel<*> (QKV / proj / FFN products, their data and weight gradients; f16x2) + "
+                                       "lvt_attn_fwd_flash_kernel / lvt_attn_bwd_flash_a / _b (flash attention on fp32 operands, per-row f16x2)", not args.no_strict_f32)
+            extra["host_fed"] = host_fed(vq, ds, max(6, args.steps // 2), world, device)
+            v1, v2 = extra["vqvae"]["clips_per_s"], extra["dsfvt"]["samples_per_s"]
+            extra["legs_combined_harmonic"] = {"clips_per_s": round(1.0 / (1.0 / v1 + 1.0 / v2), 3),
+                                               "note": "1/(1/vqvae + 1/dsfvt) of the two legs timed alone: cross-check of `value`"}
+        # the same job with every product on the plain fp32 MFMA instruction (LVT_MATH=f32), from the two legs timed alone in that mode
+        if "vqvae" in extra and "strict_f32_mfma" in extra["vqvae"] and "strict_f32_mfma" in extra["dsfvt"]:
+            f1, f2 = extra["vqvae"]["strict_f32_mfma"]["clips_per_s"], extra["dsfvt"]["strict_f32_mfma"]["samples_per_s"]
+            strict_f32 = {"clips_per_s": round(1.0 / (1.0 / f1 + 1.0 / f2), 3), "ratio_to_value": None,
+                          "note": "LVT_MATH=f32 (v_mfma_f32_32x32x2_f32 everywhere): 1/(1/vqvae + 1/dsfvt) of the two legs timed alone "
+                                  "in that mode (extra.*.strict_f32_mfma); `value` is measured in `math_mode`"}
+        if not args.no_parity and rank == 0:
+            parity, vq_enc, gate_state = vq_gates(vq, device, 8)
+            extra["vq_encode"] = vq_enc
+            parity["dsfvt_loss"] = round(float(ds_loss.detach()), 6)
+            parity["vqvae_loss"] = {k: round(float(v.detach()), 6) for k, v in losses.items()}
     if grouped:
         dist.barrier()
 
     if rank == 0:
-        del vq, ds
-        gc.enable()
-        gc.collect()
-        torch.cuda.empty_cache()
-        if not args.no_generate and world == 1:
-            extra["generate"] = generate_in_child(args)
+        if args.full:
+            del vq, ds
+            gc.enable()
+            gc.collect()
+            torch.cuda.empty_cache()
+            if not args.no_generate and world == 1:
+                extra["generate"] = generate_in_child(args)
         ms = elapsed / args.steps * 1e3
         value = clips_per_step * world * args.steps / elapsed
         if strict_f32 is not None:
@@ -955,21 +963,23 @@ def run(args):
                                    "%d distinct batches rotated; random-init weights"
                                    % (clips_per_step, vq_per_step, args.batch_clips, args.dsfvt_batch, args.batches),
                        "global_batch_clips": clips_per_step * world, "parallelism": "dp%d" % world},
-            "roofline": roofline_block(
+        }
+        if args.full:
+            out["roofline"] = roofline_block(
                 es, math_mode, "r06_combined_pmc_hbm_traffic.json",
                 "the matrix-core engine launches of the step: lvt_gemm_wide_kernel<*>, lvt_gemm_kernel<*>, lvt_conv_patch_kernel<*>, "
                 "lvt_conv_wgrad_frames_kernel<*>, lvt_attn_fwd/bwd kernels; %d launches per step, event-timed in a second "
                 "pass of the same %d steps: %.2f ms of engine time in a %.2f ms instrumented step (unperturbed: %.2f ms)"
-                % (es["launches_per_step"], args.steps, es["ms_per_step"], instrumented_ms, ms)),
-            "comm": comm,
-        }
+                % (es["launches_per_step"], args.steps, es["ms_per_step"], instrumented_ms, ms))
+            out["comm"] = comm
         if parity is not None:
             out["parity"] = parity
         if dumped is not None:
             out["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
-        out["extra"] = extra
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, gate_state)
+        if args.full:
+            out["extra"] = extra
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, gate_state)
         print(json.dumps(out), flush=True)
     if grouped:
         dist.barrier()

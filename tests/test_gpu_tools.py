@@ -1,5 +1,7 @@
 """End-to-end smoke of the drop-in drivers on the GPU: tools/train_net.py (both models, synthetic data,
-checkpoints written in the reference's layout) and scripts/generate_videos.py on the five example frames."""
+checkpoints written in the reference's layout), scripts/generate_videos.py on the five example frames and a plain
+bench.py run."""
+import json
 import os
 import subprocess
 import sys
@@ -69,3 +71,17 @@ def test_generate_videos_on_example_frames(tmp_path, golden):
     assert pngs == ["%d.png" % i for i in range(16)]
     img = np.asarray(Image.open(os.path.join(out, "7.png")))
     assert img.shape == (64, 64, 3) and img.dtype == np.uint8
+
+
+def test_bench_plain_run_prints_the_headline_only(tmp_path):
+    """A run of bench.py without --full times the step, dumps its outputs and prints the line with the contract keys; the
+    figures that take runs or checks of their own (roofline, comm, parity, extra, cpu_baseline) are left to --full."""
+    log = _run(["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "dump")],
+               timeout=600)
+    line = json.loads([ln for ln in log.splitlines() if ln.startswith("{")][-1])
+    assert line["unit"] == "clips/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["value"] > 0 and abs(line["value"] - 64 * 1e3 / line["ms_per_step"]) < 1e-3 * line["value"]
+    assert not {"roofline", "comm", "parity", "extra", "cpu_baseline"} & set(line) and line["strict_f32"] is None
+    for name in line["dump_outputs"]["arrays"]:
+        assert np.isfinite(np.load(tmp_path / "dump" / (name + ".npy"))).all(), name
