@@ -33,7 +33,7 @@ extern "C" {
 #define LVT_ENODEVICE   (-4)   /* no gfx950 device visible                             */
 
 const char *lvt_last_error(void);
-int lvt_version(void);          /* 620 = generic VQ geometry (ABI changes are listed in INTEGRATION.md) */
+int lvt_version(void);          /* 630 = batch normalisation of the conv stacks (ABI changes are listed in INTEGRATION.md) */
 /* Device probe: name, CU count, clock (kHz), HBM bytes.  Returns LVT_ENODEVICE without a GPU. */
 int lvt_device_info(char *name, int name_len, int *cus, int *clock_khz, long long *hbm_bytes);
 
@@ -565,6 +565,53 @@ int lvt_adam_step(const lvt_opt_entry *entries, int n, float beta1, float beta2,
 /* s0 = square_avg, s1 = momentum_buffer.                                                                */
 int lvt_rmsprop_step(const lvt_opt_entry *entries, int n, float alpha, float eps, float momentum,
                      void *stream);
+
+/* ---- batch normalisation of the conv stacks (nn.BatchNorm2d, NaiveSyncBatchNorm, FrozenBatchNorm2d of the reference's
+ * vidgen/layers/batch_norm.py; csrc/norm.hip).  Activations are channels-last (M = N*T*H*W rows, Cp channels), Cp = C
+ * rounded up to 4; the pad channels of every output stay exactly 0.  All reductions are deterministic (row-block partials
+ * with plain stores, combined in a fixed order in fp64; no float atomics).  Per-channel device vectors of length Cp share
+ * one layout: `stats` = (mean[Cp], biased var[Cp]) of one rank, `saved` = (mean[Cp], rstd[Cp]), `sums` = (sum g[Cp],
+ * sum g*xhat[Cp]); scale / shift are Cp floats, all 16-byte aligned.                                                      */
+#define LVT_BN_RUNNING  1   /* finalize: normalise with running_mean / running_var (eval, FrozenBN); no update       */
+#define LVT_BN_UPDATE   2   /* finalize: running = (1 - momentum) running + momentum batch                         */
+#define LVT_BN_UNBIASED 4   /* finalize: running_var receives the unbiased variance (BN); clear: the biased one (SyncBN) */
+#define LVT_BN_COUNT    8   /* finalize: *num_batches_tracked += 1                                                  */
+#define LVT_BN_TRAIN    16  /* bwd_apply: batch-statistics backward; clear: dy = scale g (running / frozen statistics) */
+/* scratch of lvt_bn_stats / lvt_bn_bwd_reduce for an (M, Cp) activation */
+size_t lvt_bn_workspace_bytes(long long M, int Cp);
+/* per-channel mean and biased variance of y (M, Cp) -> stats (2*Cp).  Each workgroup forms (mean, M2) of its tile from
+ * shifted sums (stable for any |mean| / std); a second launch merges the tiles with Chan's rule in fp64.              */
+int lvt_bn_stats(const float *y, long long M, int Cp, float *stats, void *workspace, size_t workspace_bytes, void *stream);
+/* stats: nranks consecutive (2*Cp) blocks, each over `count` rows, merged with equal weights (mean of the means; mean
+ * of the variances plus the spread of the means).  -> scale = gamma * rstd, shift = beta - mean * scale, saved =
+ * (mean, rstd), running-statistics update per `flags`.  gamma / beta / running_* have C entries.  With LVT_BN_RUNNING
+ * `stats` and `count` are ignored.  num_batches_tracked: int64 device scalar (LVT_BN_COUNT only).                       */
+int lvt_bn_finalize(const float *stats, int nranks, long long count, int C, int Cp, const float *gamma, const float *beta,
+                    float *running_mean, float *running_var, long long *num_batches_tracked, float momentum, float eps,
+                    int flags, float *scale, float *shift, float *saved, void *stream);
+/* out = act(y * scale[c] + shift[c] (+ res)), act = LVT_EPI_RELU / LVT_EPI_TANH / none (flags); res nullable.
+ * out_amax (nullable): max |out| folded in as by the engine's c_amax.                                                    */
+int lvt_bn_apply(const float *y, const float *res, long long M, int Cp, const float *scale, const float *shift, int flags,
+                 float *out, float *out_amax, void *stream);
+/* g: gradient at the normalised output (M, Cp).  -> sums = (sum g, sum g * xhat), xhat = (y - mean) * rstd from `saved`;
+ * they are also dbeta and dgamma.                                                                                       */
+int lvt_bn_bwd_reduce(const float *g, const float *y, long long M, int Cp, const float *saved, float *sums, void *workspace,
+                      size_t workspace_bytes, void *stream);
+/* dy = scale * (g - sum g / n - xhat * sum g xhat / n) with LVT_BN_TRAIN (n: rows over all ranks), else dy = scale * g
+ * (y, saved, sums unused).  dy_amax (nullable): max |dy|.                                                               */
+int lvt_bn_bwd_apply(const float *g, const float *y, long long M, int Cp, const float *scale, const float *saved,
+                     const float *sums, long long n, int flags, float *dy, float *dy_amax, void *stream);
+/* Eval fold of the normalised layers of a stack in one call (`entries`: HOST array, 16 layers per launch).  Per entry the
+ * weight is viewed as (outer, Co, inner) -- a conv weight: outer 1, inner Ci*k*k; a ConvTranspose weight: outer Cin, inner
+ * k*k -- and scale = gamma rstd, shift = beta - running_mean scale are formed from the running statistics as lvt_bn_finalize
+ * forms them (LVT_BN_RUNNING):  w_out = w * scale[co], bias_out[0..Cp) = shift (pad channels 0).  Co <= 1024.
+ * w_amax (nullable): max |w_out|.                                                                                         */
+typedef struct {
+    const float *w; float *w_out; int outer, Co, inner, Cp;
+    const float *gamma, *beta, *running_mean, *running_var; float eps;
+    float *bias_out; float *w_amax;
+} lvt_bn_fold_entry;
+int lvt_bn_fold(const lvt_bn_fold_entry *entries, int n, void *stream);
 
 #ifdef __cplusplus
 }

@@ -14,12 +14,13 @@ _LIB_PATH = os.environ.get("LVT_HIP_LIB") or os.path.join(os.path.dirname(_HERE)
 
 EPI_BIAS, EPI_RESIDUAL, EPI_RELU, EPI_TANH, EPI_MASK, EPI_ACCUM, EPI_PLANES = 1, 2, 4, 8, 16, 32, 64
 CAUSAL_KMAX, CAUSAL_KMIN, CAUSAL_TILE = 1 << 8, 1 << 9, 1 << 10      # causal attention products (include/lvt_hip.h)
-ABI_VERSION = 620           # lvt_version() of the library this module binds (argument lists below)
+ABI_VERSION = 630           # lvt_version() of the library this module binds (argument lists below)
 MATH_F32 = 1 << 16          # per-call arithmetic selectors of the engine entry points (include/lvt_hip.h)
 MATH_F16X2 = 1 << 18
 ONEHOT_DENSE = 1 << 19
 WGRAD_DB_OF_X = 1 << 20
 CONV_WEIGHT_IMAGE = 1 << 21   # the packed weight carries its f16x2 tile images behind it (lvt_conv3d_weight_images)
+BN_RUNNING, BN_UPDATE, BN_UNBIASED, BN_COUNT, BN_TRAIN = 1, 2, 4, 8, 16    # lvt_bn_finalize / lvt_bn_bwd_apply flags
 
 
 class LvtError(RuntimeError):
@@ -78,6 +79,13 @@ class PackEntry(C.Structure):
 
 class WeightImageEntry(C.Structure):
     _fields_ = [("wp", C.c_void_p), ("rows", C.c_int), ("cols", C.c_int), ("amax", C.c_void_p)]
+
+
+class BnFoldEntry(C.Structure):
+    """lvt_bn_fold_entry (include/lvt_hip.h): one normalised layer of an eval fold."""
+    _fields_ = [("w", C.c_void_p), ("w_out", C.c_void_p), ("outer", C.c_int), ("Co", C.c_int), ("inner", C.c_int),
+                ("Cp", C.c_int), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("running_mean", C.c_void_p),
+                ("running_var", C.c_void_p), ("eps", C.c_float), ("bias_out", C.c_void_p), ("w_amax", C.c_void_p)]
 
 
 class AmaxIO(C.Structure):
@@ -191,6 +199,13 @@ def _declare(lib):
         "lvt_xent_bwd": (ci, [vp, vp, cll, cll, ci, cll, ci, cll, vp, vp, vp, cf, vp, vp, vp]),
         "lvt_adam_step": (ci, [P(OptEntry), ci, cf, cf, cf, ci, vp]),
         "lvt_rmsprop_step": (ci, [P(OptEntry), ci, cf, cf, cf, vp]),
+        "lvt_bn_workspace_bytes": (sz, [cll, ci]),
+        "lvt_bn_stats": (ci, [vp, cll, ci, vp, vp, sz, vp]),
+        "lvt_bn_finalize": (ci, [vp, ci, cll, ci, ci, vp, vp, vp, vp, vp, cf, cf, ci, vp, vp, vp, vp]),
+        "lvt_bn_apply": (ci, [vp, vp, cll, ci, vp, vp, ci, vp, vp, vp]),
+        "lvt_bn_bwd_reduce": (ci, [vp, vp, cll, ci, vp, vp, vp, sz, vp]),
+        "lvt_bn_bwd_apply": (ci, [vp, vp, cll, ci, vp, vp, vp, cll, ci, vp, vp, vp]),
+        "lvt_bn_fold": (ci, [P(BnFoldEntry), ci, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)

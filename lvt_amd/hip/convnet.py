@@ -12,6 +12,12 @@ frame-resident kernels -- forward through `conv_fwd` (3x3) / `conv_fwd(wq=...)` 
 transposed passes through `conv_bwd_data(wt=...)` (3x3, as a forward convolution over transposed weights) /
 `conv_bwd_data(wph=...)` (stride 2, phase by phase), weight gradients inside `conv_bwd_weight`.  The extra
 weight packs are made next to the forward one; every other geometry takes the implicit-GEMM engine.
+
+Batch normalisation (Layer.norm, csrc/norm.hip): a normalised layer runs its conv with no bias, activation or residual
+and keeps that pre-norm output; the statistics, finalize and apply kernels then write the layer's output (activation and
+residual in the apply).  Its backward runs the BN backward (reduce + apply) between the incoming gradient and the conv's
+weight and data gradients; the residual branch still receives the gradient at the add.  A no-grad forward whose norms
+all use running statistics folds them into the conv weight and bias instead and runs the plain stack.
 """
 
 import torch
@@ -19,6 +25,7 @@ import torch
 from . import binding as L
 from . import gemm as G
 from . import ew
+from . import norm as BN
 
 class Layer:
     """One conv / ConvTranspose layer of a stack.
@@ -27,11 +34,14 @@ class Layer:
     backward-data IS this layer (Ci = out channels of the ConvTranspose, Co = its in channels).
     act: "" | "relu" | "tanh".  res_from: index of an earlier output added before the activation
     (-1: none).  ci_real / co_real: channel counts of the torch-layout weight (pads excluded).
+    norm: "" | "bn" | "syncbn" | "frozen": batch normalisation between the conv and the residual add / activation; the
+    module that holds its tensors is handed to stack_forward per call (`norms`).
     """
 
-    def __init__(self, kind, kernel, stride, pad, cin, cout, act="", res_from=-1):
+    def __init__(self, kind, kernel, stride, pad, cin, cout, act="", res_from=-1, norm=""):
         self.kind, self.kernel, self.stride, self.pad = kind, kernel, stride, pad
         self.cin, self.cout, self.act, self.res_from = cin, cout, act, res_from
+        self.norm = norm
 
     @staticmethod
     def pad4(c):
@@ -62,11 +72,68 @@ def _act_flag(act):
     return {"": 0, "relu": L.EPI_RELU, "tanh": L.EPI_TANH}[act]
 
 
-def stack_forward(layers, x, params, want_grad=True):
+def _world():
+    dist = torch.distributed
+    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+
+
+def _batch_stats(ly, nm):
+    """The layer normalises with the statistics of the batch (nn.BatchNorm2d / NaiveSyncBatchNorm in train mode)."""
+    return ly.norm in ("bn", "syncbn") and nm.training
+
+
+def _running_affine(ly, nm):
+    """(scale, shift, saved) of a layer that normalises with its running statistics (eval, FrozenBN)."""
+    co = Layer.pad4(ly.cout)
+    return BN.finalize(ly.cout, co, nm.weight, nm.bias, nm.running_mean, nm.running_var, eps=nm.eps, flags=L.BN_RUNNING)
+
+
+def _normalise(ly, nm, y, res):
+    """Statistics, finalize and apply of one normalised layer.  -> (out, (scale, saved, batch_stats, nranks))."""
+    co = Layer.pad4(ly.cout)
+    if _batch_stats(ly, nm):
+        if nm.momentum is None:
+            raise L.LvtError("BatchNorm momentum=None (cumulative average) is not implemented")
+        st = BN.stats(y)
+        nranks = _world() if ly.norm == "syncbn" else 1
+        if nranks > 1:
+            # one collective per layer: every rank fills its own slot of a zeroed (world, 2, Cp) buffer and the SUM gathers
+            # them exactly (adding zeros rounds nothing), so the merge order is the same on every rank
+            allst = torch.zeros(nranks, 2, co, dtype=torch.float32, device=y.device)
+            allst[torch.distributed.get_rank()].copy_(st)
+            torch.distributed.all_reduce(allst)
+            st, flags = allst, L.BN_UPDATE
+        else:
+            flags = L.BN_UPDATE | L.BN_UNBIASED | L.BN_COUNT
+        scale, shift, saved = BN.finalize(ly.cout, co, nm.weight, nm.bias, nm.running_mean, nm.running_var, stats=st,
+                                          nranks=nranks, count=y.numel() // co, num_batches_tracked=nm.num_batches_tracked,
+                                          momentum=nm.momentum, eps=nm.eps, flags=flags)
+        batch = True
+    else:
+        scale, shift, saved = _running_affine(ly, nm)
+        nranks, batch = 1, False
+    out = BN.apply(y, scale, shift, res=res, act=_act_flag(ly.act))
+    return out, (scale, saved, batch, nranks)
+
+
+def stack_forward(layers, x, params, want_grad=True, norms=None):
     """x: (N,T,H,W,C) channels-last.  params: [(weight, bias)] in torch layout.  want_grad: a backward pass will follow
-    (the transposed weight packs it needs are made here, next to the forward ones).
+    (the transposed weight packs it needs are made here, next to the forward ones).  norms: per layer, the module holding
+    its batch-normalisation tensors (None: no norm anywhere).
     Returns (outs, saved) where outs[i] is the post-activation output of layer i."""
     outs, geoms, packed = [], [], []
+    norms = norms if norms is not None else [None] * len(layers)
+    # eval fold: a forward without backward whose norms all use running statistics folds them into the conv weight and
+    # bias (w' = w scale, b' = shift) and then runs exactly the kernels of the plain stack
+    if not want_grad and all(nm is None or not _batch_stats(ly, nm) for ly, nm in zip(layers, norms)):
+        todo = [i for i, nm in enumerate(norms) if nm is not None]
+        if todo:
+            params = list(params)
+            folded = BN.fold([(params[i][0].detach(), layers[i].kind == "convT", norms[i], Layer.pad4(layers[i].cout))
+                              for i in todo])          # one launch for the whole stack
+            for i, wb in zip(todo, folded):
+                params[i] = wb
+        norms = [None] * len(layers)
     # every weight pack of the stack in ONE launch up front (24 ~5 us launches per VQ-VAE pass otherwise, each in front of the
     # layer that needs it): the geometries follow from the shapes alone
     pb = G.PackBatch()
@@ -95,11 +162,24 @@ def stack_forward(layers, x, params, want_grad=True):
         packed.append((wp, wt, wph, wq))
     pb.launch()
     cur = x
+    pre, bn_saved = [None] * len(layers), [None] * len(layers)
     for i, (ly, (w, b)) in enumerate(zip(layers, params)):
         g, (wp, wt, wph, wq) = geoms[i], packed[i]
+        nm = norms[i]
         seen = (g.N, g.Ti, g.Hi, g.Wi) if ly.kind == "conv" else (g.N, g.To, g.Ho, g.Wo)
         assert seen == tuple(cur.shape[:4]), "geometry of the pre-pass does not match the activation"
         res = outs[ly.res_from] if ly.res_from >= 0 else None
+        if nm is not None:
+            # the conv alone; bias, residual and activation belong to the normalised output
+            if ly.kind == "conv":
+                y = G.conv_fwd(g, cur, wp, wq=wq)
+            else:
+                y = G.conv_bwd_data(g, cur, wp, wph=wph)
+            pre[i] = y
+            y, bn_saved[i] = _normalise(ly, nm, y, res)
+            outs.append(y)
+            cur = y
+            continue
         bias = _padded_bias(ly, b)
         if ly.kind == "conv":
             y = G.conv_fwd(g, cur, wp, bias=bias, res=res, flags=_act_flag(ly.act), wq=wq)
@@ -110,12 +190,31 @@ def stack_forward(layers, x, params, want_grad=True):
             y = G.conv_bwd_data(g, cur, wp, bias=bias, res=res, flags=_act_flag(ly.act), wph=wph)
         outs.append(y)
         cur = y
-    return outs, (geoms, packed)
+    return outs, (geoms, packed, norms, pre, bn_saved)
+
+
+def _bn_backward(ly, nm, gp, y, bn_saved):
+    """BN backward of one layer: gp is the gradient at the normalised output (mask and residual already folded in).
+    -> (gradient at the conv output, (dgamma, dbeta) or None)."""
+    scale, saved, batch, nranks = bn_saved
+    co = Layer.pad4(ly.cout)
+    if ly.norm == "frozen":
+        return BN.bwd_apply(gp, None, scale, train=False), None
+    sums = BN.bwd_reduce(gp, y, saved)
+    dg = (sums[1, :ly.cout].clone(), sums[0, :ly.cout].clone())
+    if not batch:
+        return BN.bwd_apply(gp, None, scale, train=False), dg
+    if nranks > 1:
+        # the statistics' gradients summed over the ranks (the reference's AllReduce.backward): one collective per layer
+        sums = sums.clone()
+        torch.distributed.all_reduce(sums)
+    return BN.bwd_apply(gp, y, scale, saved, sums, n=nranks * (y.numel() // co), train=True), dg
 
 
 def stack_backward(layers, x, outs, saved, grad_out, need_input_grad=False):
-    """grad_out: dL/d(outs[-1]) (post-activation).  Returns (grad_x or None, [(dw, db)])."""
-    geoms, packed = saved
+    """grad_out: dL/d(outs[-1]) (post-activation).  Returns (grad_x or None, [(dw, db)], [(dgamma, dbeta)]); db is None for
+    a normalised layer, and the last list holds the layers with trainable norms in stack order."""
+    geoms, packed, norms, pre, bn_saved = saved
     n = len(layers)
     # g_pre of the last layer
     last = layers[-1]
@@ -130,20 +229,30 @@ def stack_backward(layers, x, outs, saved, grad_out, need_input_grad=False):
     gpres = [None] * n
     gpres[n - 1] = gpre
     grads = [None] * n
+    norm_grads = [None] * n
+    gx = None
     for i in range(n - 1, -1, -1):
         ly, g, (wp, wt, wph, wq) = layers[i], geoms[i], packed[i]
         inp = outs[i - 1] if i > 0 else x
         gp = gpres[i]
+        if norms[i] is not None:
+            gp, norm_grads[i] = _bn_backward(ly, norms[i], gp, pre[i], bn_saved[i])
         # parameter gradients
         co = Layer.pad4(ly.cout)
         db = None
-        if ly.kind == "conv":
+        if norms[i] is not None:
+            # a normalised conv has no bias
+            if ly.kind == "conv":
+                dw = G.conv_bwd_weight(g, inp, gp, ly.cin, ly.cout)
+            else:
+                dw = G.conv_bwd_weight(g, gp, inp, ly.cout, ly.cin)
+        elif ly.kind == "conv":
             dw, db = G.conv_bwd_weight(g, inp, gp, ly.cin, ly.cout, want_bias=True)     # db rides on the dy stream
         else:
             # transposed layer: the same call with the operands swapped; its bias gradient is the column sum of gp, which the
             # stride-2 frame-resident kernel adds up from the patches it stages
             dw, db = G.conv_bwd_weight(g, gp, inp, ly.cout, ly.cin, want_bias=True, bias_of_x=True)
-        if db is None:
+        if norms[i] is None and db is None:
             db = G.colsum(gp, gp.numel() // co, co)[:ly.cout]
         grads[i] = (dw, db)      # dw is (Co, Ci, Kt, Kh, Kw); callers view it as the parameter shape
         # gradient w.r.t. the layer input == g_pre of layer i-1 (mask / residual folded in)
@@ -161,5 +270,5 @@ def stack_backward(layers, x, outs, saved, grad_out, need_input_grad=False):
         if i > 0:
             gpres[i - 1] = gin
         else:
-            return gin, grads
-    return None, grads
+            gx = gin
+    return gx, grads, [d for d in norm_grads if d is not None]

@@ -285,7 +285,8 @@ class PackBatch:
         _same_amax(dst, w)
         if extra:
             ie = L.WeightImageEntry()
-            ie.wp, ie.rows, ie.cols, ie.amax = dst.data_ptr(), rows, cols, L.amax_of(dst).data_ptr()
+            # the record of dst is w's (same slot); looked up on w: dst is not written until launch()
+            ie.wp, ie.rows, ie.cols, ie.amax = dst.data_ptr(), rows, cols, L.amax_of(w).data_ptr()
             self.images.append(ie)
             self.keep.append(dst)
             dst._lvt_wimg = True

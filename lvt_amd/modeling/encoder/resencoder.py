@@ -31,14 +31,16 @@ class ResEncoder(Encoder):
         convstack.check_norm(norm, use_spectral_norm)
         if out_activation != "":
             raise NotImplementedError("ResEncoder out_activation %r is not used by any shipped config" % out_activation)
+        norm = norm or ""
+        nl = convstack.norm_layer
         if stride == 4:
-            mods = [nn.Conv2d(in_channels, nf // 2, 4, 2, 1), nn.ReLU(True), nn.Conv2d(nf // 2, nf, 4, 2, 1),
-                    nn.ReLU(True), nn.Conv2d(nf, nf, 3, 1, 1)]
+            mods = [nl(nn.Conv2d(in_channels, nf // 2, 4, 2, 1), norm), nn.ReLU(True), nl(nn.Conv2d(nf // 2, nf, 4, 2, 1), norm),
+                    nn.ReLU(True), nl(nn.Conv2d(nf, nf, 3, 1, 1), norm)]
         elif stride == 2:
-            mods = [nn.Conv2d(in_channels, nf // 2, 4, 2, 1), nn.ReLU(True), nn.Conv2d(nf // 2, nf, 3, 1, 1)]
+            mods = [nl(nn.Conv2d(in_channels, nf // 2, 4, 2, 1), norm), nn.ReLU(True), nl(nn.Conv2d(nf // 2, nf, 3, 1, 1), norm)]
         else:
             raise ValueError
-        mods += [convstack.ResBlock(nf, res_channels) for _ in range(n_layers)]
+        mods += [convstack.ResBlock(nf, res_channels, norm) for _ in range(n_layers)]
         self.layers = nn.Sequential(*mods)
         self.in_channels, self.out_channels = in_channels, nf
         self._plan = self._build_plan()
@@ -46,30 +48,37 @@ class ResEncoder(Encoder):
     def _build_plan(self):
         """Translate the module list into fused engine layers + the (weight, bias) modules they use."""
         mods = list(self.layers)
-        plan, owners = [], []
+        plan, owners, norms = [], [], []
         for i, m in enumerate(mods):
             nxt = mods[i + 1] if i + 1 < len(mods) else None
             # this output is rectified if an explicit ReLU or a ResBlock (in-place ReLU) follows
             relu_after = isinstance(nxt, (nn.ReLU, convstack.ResBlock))
-            if isinstance(m, nn.Conv2d):
+            if convstack.is_conv(m, nn.Conv2d):
+                m, nm, kind = convstack.split_norm(m)
                 k, s, p = m.kernel_size[0], m.stride[0], m.padding[0]
                 plan.append(Layer("conv", (1, k, k), (1, s, s), (0, p, p), m.in_channels, m.out_channels,
-                                  act="relu" if relu_after else ""))
+                                  act="relu" if relu_after else "", norm=kind))
                 owners.append(m)
+                norms.append(nm)
             elif isinstance(m, convstack.ResBlock):
-                c3, c1 = m.block[1], m.block[3]
+                (c3, n3, k3), (c1, n1, k1) = convstack.split_norm(m.block[1]), convstack.split_norm(m.block[3])
                 src = len(plan) - 1          # output index of the (rectified) block input
-                plan.append(Layer("conv", (1, 3, 3), (1, 1, 1), (0, 1, 1), c3.in_channels, c3.out_channels, act="relu"))
+                plan.append(Layer("conv", (1, 3, 3), (1, 1, 1), (0, 1, 1), c3.in_channels, c3.out_channels, act="relu",
+                                  norm=k3))
                 owners.append(c3)
+                norms.append(n3)
+                # the residual is added after the second norm: relu(x) + BN(conv1x1(relu(BN(conv3x3(relu(x))))))
                 plan.append(Layer("conv", (1, 1, 1), (1, 1, 1), (0, 0, 0), c1.in_channels, c1.out_channels,
-                                  act="relu" if relu_after else "", res_from=src))
+                                  act="relu" if relu_after else "", res_from=src, norm=k1))
                 owners.append(c1)
+                norms.append(n1)
         self._owners = owners
+        self._norms = norms if any(n is not None for n in norms) else None      # NORM "": the plain stack, as before
         return plan
 
     def forward_cl(self, x_cl):
         """(N,1,H,W,Cin_pad4) channels-last -> (N,1,H/4,W/4,nf)."""
-        return convstack.run_stack(x_cl, self._plan, [(m.weight, m.bias) for m in self._owners])
+        return convstack.run_stack(x_cl, self._plan, [(m.weight, m.bias) for m in self._owners], self._norms)
 
     def forward(self, x):
         """(N,C,H,W) -> (N,nf,H/4,W/4), the reference's layout contract."""

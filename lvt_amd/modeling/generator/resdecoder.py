@@ -26,14 +26,18 @@ class ResDecoder(Generator):
                  out_activation, stride):
         super().__init__()
         convstack.check_norm(norm, use_spectral_norm)
-        mods = [nn.Conv2d(in_channels, nf, 3, 1, 1)]
-        mods += [convstack.ResBlock(nf, res_channels) for _ in range(n_layers)]
+        norm = norm or ""
+        nl = convstack.norm_layer
+        mods = [nl(nn.Conv2d(in_channels, nf, 3, 1, 1), norm)]
+        mods += [convstack.ResBlock(nf, res_channels, norm) for _ in range(n_layers)]
         mods.append(nn.ReLU(True))
         if stride == 4:
-            mods += [nn.ConvTranspose2d(nf, nf // 2, 4, 2, 1), nn.ReLU(True),
+            # the last ConvTranspose is never normalised (resdecoder.py:55-59)
+            mods += [nl(nn.ConvTranspose2d(nf, nf // 2, 4, 2, 1), norm), nn.ReLU(True),
                      nn.ConvTranspose2d(nf // 2, out_channels, 4, 2, 1)]
         elif stride == 2:
-            mods += [nn.ConvTranspose2d(nf, out_channels, 4, 2, 1)]
+            # ... except at stride 2, where it is the only one and the reference normalises it (resdecoder.py:60-63)
+            mods += [nl(nn.ConvTranspose2d(nf, out_channels, 4, 2, 1), norm)]
         else:
             raise ValueError
         if out_activation == "tanh":
@@ -46,7 +50,7 @@ class ResDecoder(Generator):
 
     def _build_plan(self):
         mods = list(self.layers)
-        plan, owners = [], []
+        plan, owners, norms = [], [], []
         for i, m in enumerate(mods):
             nxt = mods[i + 1] if i + 1 < len(mods) else None
             if isinstance(nxt, (nn.ReLU, convstack.ResBlock)):
@@ -55,28 +59,31 @@ class ResDecoder(Generator):
                 act = "tanh"
             else:
                 act = ""
-            if isinstance(m, nn.Conv2d):
+            if convstack.is_conv(m, nn.Conv2d) or convstack.is_conv(m, nn.ConvTranspose2d):
+                m, nm, kind = convstack.split_norm(m)
                 k, s, p = m.kernel_size[0], m.stride[0], m.padding[0]
-                plan.append(Layer("conv", (1, k, k), (1, s, s), (0, p, p), m.in_channels, m.out_channels, act=act))
+                plan.append(Layer("convT" if isinstance(m, nn.ConvTranspose2d) else "conv", (1, k, k), (1, s, s), (0, p, p),
+                                  m.in_channels, m.out_channels, act=act, norm=kind))
                 owners.append(m)
-            elif isinstance(m, nn.ConvTranspose2d):
-                k, s, p = m.kernel_size[0], m.stride[0], m.padding[0]
-                plan.append(Layer("convT", (1, k, k), (1, s, s), (0, p, p), m.in_channels, m.out_channels, act=act))
-                owners.append(m)
+                norms.append(nm)
             elif isinstance(m, convstack.ResBlock):
-                c3, c1 = m.block[1], m.block[3]
+                (c3, n3, k3), (c1, n1, k1) = convstack.split_norm(m.block[1]), convstack.split_norm(m.block[3])
                 src = len(plan) - 1
-                plan.append(Layer("conv", (1, 3, 3), (1, 1, 1), (0, 1, 1), c3.in_channels, c3.out_channels, act="relu"))
+                plan.append(Layer("conv", (1, 3, 3), (1, 1, 1), (0, 1, 1), c3.in_channels, c3.out_channels, act="relu",
+                                  norm=k3))
                 owners.append(c3)
+                norms.append(n3)
                 plan.append(Layer("conv", (1, 1, 1), (1, 1, 1), (0, 0, 0), c1.in_channels, c1.out_channels, act=act,
-                                  res_from=src))
+                                  res_from=src, norm=k1))
                 owners.append(c1)
+                norms.append(n1)
         self._owners = owners
+        self._norms = norms if any(n is not None for n in norms) else None      # NORM "": the plain stack, as before
         return plan
 
     def forward_cl(self, z_cl):
         """(N,1,h,w,Cin) channels-last -> (N,1,4h,4w,Cout_pad4)."""
-        return convstack.run_stack(z_cl, self._plan, [(m.weight, m.bias) for m in self._owners])
+        return convstack.run_stack(z_cl, self._plan, [(m.weight, m.bias) for m in self._owners], self._norms)
 
     def forward(self, z):
         y = self.forward_cl(convstack._LayoutIn.apply(z))
