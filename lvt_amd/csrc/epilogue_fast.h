@@ -62,6 +62,9 @@ struct LvtRowIdentity { __device__ __forceinline__ long long operator()(int row)
 template <int F, int TM, int TN, class RM = LvtRowIdentity>
 __device__ __forceinline__ float lvt_epi_fast_wave(const LvtEpi &e, lvt_f32x16 (&acc)[TM][TN], float *wave_tile, int m_w, int n_w,
                                                    int lane, const RM rm = RM()) {
+    // no fused multiply-add across the epilogue steps: alpha acc, + bias, + res are rounded one by one, as in lvt_epilogue_vec and
+    // the scalar lvt_epilogue (a contraction the compiler makes in one form only breaks their bit identity for alpha != 1)
+#pragma clang fp contract(off)
     static_assert(TM == 2 && TN == 2, "64 x 64 sub-tiles");
     constexpr int SW = TN * 32;
     const int flags = F >= 0 ? F : e.flags;

@@ -726,6 +726,7 @@ struct PatchTRows { int cls; __device__ __forceinline__ long long operator()(int
 template <int AMODE, int BM, int BN, int WM, int WN>
 __device__ __forceinline__ void lvt_epilogue(const KParams &p, f32x16 (&acc)[BM / WM / 32][BN / WN / 32], int m0, int n0,
                                              int wm, int wn, int l31, int half, int cls, long long coff, int z, int split) {
+#pragma clang fp contract(off)      // (the epilogue steps round one by one in every form: epilogue_fast.h)
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
     // ConvTranspose phase: decode the phase-ordered row into the channels-last dx row.
     int fw = 0, fh = 0, ft = 0, rt = 0, rh = 0, rw = 0;
@@ -845,6 +846,7 @@ template <int AMODE, int BM, int BN, int WM, int WN>
 __device__ __forceinline__ void lvt_epilogue_vec(const KParams &p, f32x16 (&acc)[BM / WM / 32][BN / WN / 32], float *lds,
                                                  int m0, int n0, int wm, int wn, int lane, int cls, long long coff, int z,
                                                  int split) {
+#pragma clang fp contract(off)      // (the epilogue steps round one by one in every form: epilogue_fast.h)
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
     constexpr int SW = TN * 32;                    // sub-tile width (floats), row stride of the LDS turn-table
     constexpr int C4 = SW / 4;                     // float4 per row

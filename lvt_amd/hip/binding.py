@@ -253,6 +253,7 @@ def set_math_mode(mode):
     if mode not in MATH_MODES:
         raise LvtError("math mode must be one of %s (got %r)" % (MATH_MODES, mode))
     _math_mode = mode
+    bump_epoch()              # launches of the other arithmetics make no records: nothing recorded before may be trusted
 
 
 def get_math_mode():
@@ -270,17 +271,23 @@ def f16x2():
 # ---- max |.| bookkeeping of the f16x2 arithmetic -------------------------------------------------------------------
 # Every operand of an f16x2 engine launch needs a device scalar >= max |operand|.  Engine launches report the max of what
 # they write (c_amax), the helper kernels that produce engine operands do the same, and anything else falls back to one
-# lvt_amax pass.  The scalar rides on the tensor object as `_lvt_amax = (slot, version, epoch, data_ptr)`: a torch in-place
-# op bumps `_version`, `p.data = ...` changes the pointer, and whatever rewrites tensors behind torch's back bumps the epoch
-# (the fused optimizers after a step; the meta-architectures at the start of every forward, which also covers parameters
-# edited through `.data` between passes) -- any of them invalidates the record.
+# lvt_amax pass.  The scalar rides on the tensor object as `_lvt_amax = (slot, version, epoch, data_ptr, storage, gen, lo,
+# hi)`: a torch in-place op bumps `_version`, `p.data = ...` changes the pointer, and whatever rewrites tensors behind torch's
+# back bumps the epoch (the fused optimizers after a step; the meta-architectures at the start of every forward, which also
+# covers parameters edited through `.data` between passes) -- any of them invalidates the record.  Writes of the wrappers
+# through raw pointers (new_amax, drop_amax) are logged per storage as (generation, byte range): a record made at generation
+# `gen` is stale once a later write overlaps its bytes [lo, hi), whichever view of the storage (the base included) the write
+# went through -- torch's `_version` sees none of them.
 _amax_pool, _amax_pos, _epoch = None, 0, 0
+_wgen, _wlog = 0, {}          # write generation; storage data_ptr -> [floor, [(gen, lo, hi), ...]] (records below floor: stale)
+_WLOG_MAX = 64
 
 
 def bump_epoch():
     """Called by whatever rewrites tensors behind torch's back (the fused optimizers): forget every cached max |.|."""
     global _epoch
     _epoch += 1
+    _wlog.clear()             # (records of older epochs are invalid anyway)
 
 
 def amax_slot(device):
@@ -293,27 +300,55 @@ def amax_slot(device):
     return s
 
 
-def set_amax(t, slot):
-    t._lvt_amax = (slot, t._version, _epoch, t.data_ptr())
+def _extent(t):
+    """(storage data_ptr, first byte, end byte, covers the whole storage) of what `t` addresses."""
+    st = t.untyped_storage()
+    key, lo = st.data_ptr(), t.data_ptr()
+    span = 1
+    for n, s in zip(t.shape, t.stride()):
+        if n == 0:
+            return key, lo, lo, False
+        span += (n - 1) * s
+    hi = lo + span * t.element_size()
+    return key, lo, hi, lo <= key and hi >= key + st.nbytes()
+
+
+def _note_write(t):
+    """Log a raw-pointer write of `t`: every record on the same storage whose bytes it overlaps is stale from now on."""
+    global _wgen
+    _wgen += 1
+    key, lo, hi, whole = _extent(t)
+    if whole:
+        _wlog[key] = [_wgen, []]
+    else:
+        log = _wlog.setdefault(key, [0, []])
+        log[1].append((_wgen, lo, hi))
+        if len(log[1]) > _WLOG_MAX:
+            log[0] = log[1].pop(0)[0]     # forget the oldest write: records made before it are no longer trusted
+    return key, lo, hi
+
+
+def set_amax(t, slot, _ext=None):
+    key, lo, hi = _ext if _ext is not None else _extent(t)[:3]
+    t._lvt_amax = (slot, t._version, _epoch, t.data_ptr(), key, _wgen, lo, hi)
     return t
 
 
 def drop_amax(t):
     """EVERY wrapper of a kernel that rewrites a tensor in place through its raw pointer must call this (torch's `_version`
-    does not see such writes): the record of `t` and of the tensor it is a view of are forgotten.  LVT_AMAX_CHECK=1 verifies
-    every record that is used against the tensor (a debugging aid: it synchronises with the device on every engine call)."""
-    if getattr(t, "_lvt_amax", None) is not None:
-        t._lvt_amax = None
-    base = getattr(t, "_base", None)
-    if base is not None and getattr(base, "_lvt_amax", None) is not None:
-        base._lvt_amax = None
+    does not see such writes): the record of `t` and every record of another view of its storage (its base included) that
+    covers bytes of `t` are forgotten.  LVT_AMAX_CHECK=1 verifies every record that is used against the tensor (a debugging
+    aid: it synchronises with the device on every engine call)."""
+    t._lvt_amax = None
+    _note_write(t)
 
 
 AMAX_CHECK = bool(os.environ.get("LVT_AMAX_CHECK"))
 
 
 def _checked(slot, t):
-    if AMAX_CHECK:
+    # (launches recorded into a hipGraph are not checked: reading the slot would synchronise inside the capture)
+    if AMAX_CHECK and not torch.cuda.is_current_stream_capturing():
         have, real = float(slot), float(t.detach().abs().max()) if t.numel() else 0.0
         if not have >= real:
             raise LvtError("stale max |.| record: %g recorded, %g in the tensor of shape %s (an in-place kernel wrapper that "
@@ -323,15 +358,27 @@ def _checked(slot, t):
 
 def _valid_amax(t):
     rec = getattr(t, "_lvt_amax", None)
-    if rec is not None and rec[1] == t._version and rec[2] == _epoch and rec[3] == t.data_ptr():
-        return rec[0]
-    return None
+    if rec is None or rec[1] != t._version or rec[2] != _epoch or rec[3] != t.data_ptr():
+        return None
+    log = _wlog.get(rec[4])
+    if log is not None:
+        gen = rec[5]
+        if gen < log[0]:
+            return None
+        for g, lo, hi in reversed(log[1]):
+            if g <= gen:
+                break
+            if lo < rec[7] and rec[6] < hi:
+                return None
+    return rec[0]
 
 
 def new_amax(t):
-    """Attach a fresh zeroed slot to `t` (about to be written by a launch that reports max |t| into it) and return it."""
+    """Attach a fresh zeroed slot to `t` (about to be written by a launch that reports max |t| into it) and return it.
+    The write is logged: records of other views of the storage that overlap `t` are stale from now on."""
+    ext = _note_write(t)
     slot = amax_slot(t.device)
-    set_amax(t, slot)
+    set_amax(t, slot, ext)
     return slot
 
 
@@ -366,8 +413,11 @@ def amax_of(t):
 
 def out_amax(t):
     """Pointer argument for a helper kernel that can report max |t| of the tensor it is about to write: a fresh slot
-    attached to `t` in f16x2 mode, NULL otherwise."""
-    return ptr(new_amax(t)) if _math_mode == "f16x2" else None
+    attached to `t` in f16x2 mode, NULL otherwise (and the old record of `t` is dropped: the launch rewrites it)."""
+    if _math_mode == "f16x2":
+        return ptr(new_amax(t))
+    drop_amax(t)
+    return None
 
 
 def amax_prefetch(tensors):
@@ -432,8 +482,11 @@ AMAX_FALLBACKS = [0]        # diagnostic: stand-alone lvt_amax passes issued so 
 
 def amax_io(a=None, b=None, c=None):
     """lvt_amax_io for an engine call: operands a, b (tensors; looked up only in f16x2 mode), result c (tensor that the
-    launch is about to write).  Returns None outside f16x2 mode (the entry points take a NULL pointer)."""
+    launch is about to write).  Returns None outside f16x2 mode (the entry points take a NULL pointer; c's old record is
+    dropped)."""
     if _math_mode != "f16x2":
+        if c is not None:
+            drop_amax(c)
         return None
     io = AmaxIO()
     io.a = amax_of(a).data_ptr() if a is not None else None

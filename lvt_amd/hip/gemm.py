@@ -40,6 +40,8 @@ def gemm(A, B, C_out, M, N, K, ta=0, tb=0, lda=None, ldb=None, ldc=None, a_kb=0,
         d.b_amax2 = L.amax_of(b_also).data_ptr() if b_also is not None else None
         if splits <= 1 and C_out.dtype == torch.float32:
             d.c_amax = L.new_amax(C_out).data_ptr()
+    if not d.c_amax:
+        L.drop_amax(C_out)            # a launch that makes no record (split-K, PLANES, other arithmetic) still rewrites C
     lib = L.lib()
     ws, nws = None, 0
     if splits > 1:
@@ -165,6 +167,7 @@ def gemm_small(A, B, C_out, M, N, K, tb=0, lda=None, ldb=None, ldc=None, batch=1
         return gemm(A, B, C_out, M, N, K, ta=0, tb=tb, lda=lda, ldb=ldb, ldc=ldc, batch_inner=batch, sB=(0, sB),
                     sC=(0, sC), alpha=alpha, flags=flags, bias=bias, res=res, ldr=ldr)
     splits = _smallm_splits(N, K) if (tb == 0 and batch == 1 and N % 4 == 0) else 1
+    L.drop_amax(C_out)                # (the decode kernels report no max |C|)
     if splits > 1:
         lib = L.lib()
         nws = lib.lvt_gemm_smallm_splitk_workspace_bytes(M, N, splits)
