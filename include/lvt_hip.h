@@ -33,7 +33,7 @@ extern "C" {
 #define LVT_ENODEVICE   (-4)   /* no gfx950 device visible                             */
 
 const char *lvt_last_error(void);
-int lvt_version(void);          /* 630 = batch normalisation of the conv stacks (ABI changes are listed in INTEGRATION.md) */
+int lvt_version(void);          /* 640 = block-local decode attention (ABI changes are listed in INTEGRATION.md) */
 /* Device probe: name, CU count, clock (kHz), HBM bytes.  Returns LVT_ENODEVICE without a GPU. */
 int lvt_device_info(char *name, int name_len, int *cus, int *clock_khz, long long *hbm_bytes);
 
@@ -483,6 +483,16 @@ int lvt_attn_bwd_flash(const float *q, const float *k, const float *v, const flo
 int lvt_attn_decode(const float *q, long long ldq, const float *Kc, const float *Vc, int B, int H, int S, int da, int qi,
                     float temper, const float *dt, const float *dh, const float *dw, int bt, int bh, int bw,
                     float *o, const int *pos, long long q_pos, void *stream);
+/* the same for a slice (st,sh,sw) whose attention runs inside blocks (bt,bh,bw) (the block-split branch of
+ * vt_attention.py:189-200): the caches stay token-major in SLICE raster order, (B, S, H*da) with S = st*sh*sw.  The query at slice
+ * position qi (or pos[0], clamped to [0, S)) attends the tokens of its own block that are at or before it in the block's raster
+ * order -- local key (t',h',w') is cache row ((ot+t')*sh + oh+h')*sw + ow+w' with (ot,oh,ow) the block's origin -- and the
+ * dt/dh/dw banks (H rows of 2*bt-1 / 2*bh-1 / 2*bw-1) are indexed by coordinate differences inside the block.  Limits: da == 128;
+ * every block extent divides its slice extent; bt*bh*bw <= 1024 keys per query; S <= INT_MAX (the caches are the caller's).
+ * bt,bh,bw == st,sh,sw computes exactly what lvt_attn_decode does.  Fixed summation order, no atomics.                 */
+int lvt_attn_decode_blocks(const float *q, long long ldq, const float *Kc, const float *Vc, int B, int H, int da, int qi,
+                           float temper, const float *dt, const float *dh, const float *dw, int st, int sh, int sw,
+                           int bt, int bh, int bw, float *o, const int *pos, long long q_pos, void *stream);
 
 /* integer plumbing of a decode step driven by a device-side cursor (the reference indexes python ints: vt.py:121-131).
  * codes (rows, S1) int64 with S1 = S + 1: the slice being decoded, one always-padded extra slot per row.

@@ -601,18 +601,26 @@ extern "C" int lvt_xent_bwd(const float *logits, const long long *target, long l
 // Same arithmetic as row i of the full causal layer (the masked columns j > i carry exp(-1e4 - m) == 0).
 // Scores: 16 lanes per key (coalesced rows).  P.V: the keys are dealt to the 4 waves (j = w mod 4), every
 // lane owns 2 of the 128 output dims, and the 4 partial sums are added in wave order through LDS.
+//
+// The keys of a query are those of ITS attention block, enumerated in the block's raster order up to the query itself
+// (local index j = 0..li).  MODE says where local key j lives in the slice-ordered cache:
+//   0  the block is the whole slice (lvt_attn_decode): row j.
+//   1  blocks split the leading axis only: a block is one contiguous run of cache rows, row = block origin + j.
+//   2  blocks split the inner axes too: row ((ot+tj)*sh + oh+hj)*sw + ow+wj, kept in an LDS table for the P.V pass.
+// `g` is the block (bias banks, at most 1024 keys: ps[]), `vol` the slice (MODE 0: unused); S = rows of the cache.
 // ------------------------------------------------------------------------------------------------
 #define DEC_DA 128
 #define DEC_WAVES 4
-__global__ __launch_bounds__(64 * DEC_WAVES) void lvt_attn_decode_kernel(const float *__restrict__ q, long long ldq,
-                                                             const float *__restrict__ Kc,
-                                                             const float *__restrict__ Vc, int H, int S, int qi,
-                                                             float temper, const float *__restrict__ dt,
-                                                             const float *__restrict__ dh, const float *__restrict__ dw,
-                                                             BiasGeom g, float *__restrict__ o,
-                                                             const int *__restrict__ pos, long long q_pos) {
+#define DEC_MAXKEYS 1024
+template <int MODE>
+__device__ __forceinline__ void attn_decode_body(const float *__restrict__ q, long long ldq, const float *__restrict__ Kc,
+                                                 const float *__restrict__ Vc, int H, int S, int qi, float temper,
+                                                 const float *__restrict__ dt, const float *__restrict__ dh,
+                                                 const float *__restrict__ dw, BiasGeom g, BiasGeom vol,
+                                                 float *__restrict__ o, const int *__restrict__ pos, long long q_pos) {
     __shared__ float qs[DEC_DA];
-    __shared__ float ps[1024];
+    __shared__ float ps[DEC_MAXKEYS];
+    __shared__ int rw[MODE == 2 ? DEC_MAXKEYS : 1];                      // MODE 2: cache row of local key j
     __shared__ float redm[DEC_WAVES], reds[DEC_WAVES];
     __shared__ float acc[DEC_WAVES][DEC_DA];
     const int b = blockIdx.x / H, h = blockIdx.x % H, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -625,8 +633,18 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void lvt_attn_decode_kernel(const f
     const float *qp = q + (long long)b * ldq + h * DEC_DA;
     if (tid < DEC_DA) qs[tid] = qp[tid];
     __syncthreads();
-    const int nk = qi + 1;
-    const int wi = qi % g.bw, hi = (qi / g.bw) % g.bh, ti = qi / (g.bw * g.bh);
+    int wi = qi % g.bw, hi = (qi / g.bw) % g.bh, ti = qi / (g.bw * g.bh);
+    int ot = 0, oh = 0, ow = 0;                                         // origin of the query's block in the slice
+    if (MODE != 0) {
+        const int wq = qi % vol.bw, hq = (qi / vol.bw) % vol.bh, tq = qi / (vol.bw * vol.bh);
+        wi = wq % g.bw; hi = hq % g.bh; ti = tq % g.bt;
+        ot = tq - ti; oh = hq - hi; ow = wq - wi;
+    }
+    if (MODE == 1) {                                                    // oh == ow == 0: the block's rows are contiguous
+        const long long skip = (long long)ot * vol.bh * vol.bw * hd;
+        Kc += skip; Vc += skip;
+    }
+    const int nk = MODE == 0 ? qi + 1 : (ti * g.bh + hi) * g.bw + wi + 1;
     const float *bt = dt + h * (2 * g.bt - 1), *bhp = dh + h * (2 * g.bh - 1), *bwp = dw + h * (2 * g.bw - 1);
     float m = -3.4e38f;
     // scores: 16 lanes share one key (a coalesced 512-byte row: 8 dims = two float4 per lane), 16 keys per pass of
@@ -638,9 +656,11 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void lvt_attn_decode_kernel(const f
         for (int d = 0; d < 8; ++d) qv[d] = qs[sub * 8 + d];
         for (int j0 = 0; j0 < nk; j0 += 16) {
             const int j = j0 + grp;
+            const int wj = j % g.bw, hj = (j / g.bw) % g.bh, tj = j / (g.bw * g.bh);
+            const int row = MODE == 2 ? ((ot + tj) * vol.bh + oh + hj) * vol.bw + ow + wj : j;
             float sc = 0.f;
             if (j < nk) {
-                const float4 *kp = reinterpret_cast<const float4 *>(Kc + ((long long)b * S + j) * hd + h * DEC_DA + sub * 8);
+                const float4 *kp = reinterpret_cast<const float4 *>(Kc + ((long long)b * S + row) * hd + h * DEC_DA + sub * 8);
                 const float4 k0 = kp[0], k1 = kp[1];
                 sc = fmaf(qv[0], k0.x, sc); sc = fmaf(qv[1], k0.y, sc); sc = fmaf(qv[2], k0.z, sc); sc = fmaf(qv[3], k0.w, sc);
                 sc = fmaf(qv[4], k1.x, sc); sc = fmaf(qv[5], k1.y, sc); sc = fmaf(qv[6], k1.z, sc); sc = fmaf(qv[7], k1.w, sc);
@@ -648,9 +668,9 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void lvt_attn_decode_kernel(const f
 #pragma unroll
             for (int d = 8; d > 0; d >>= 1) sc += __shfl_xor(sc, d, 64);
             if (sub == 0 && j < nk) {
-                const int wj = j % g.bw, hj = (j / g.bw) % g.bh, tj = j / (g.bw * g.bh);
                 const float x = sc / temper + ((bt[ti - tj + g.bt - 1] + bhp[hi - hj + g.bh - 1]) + bwp[wi - wj + g.bw - 1]);
                 ps[j] = x;
+                if (MODE == 2) rw[j] = row;
                 m = fmaxf(m, x);
             }
         }
@@ -675,7 +695,8 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void lvt_attn_decode_kernel(const f
         const float *v0 = vp + (long long)j * hd;
         float2 x[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) x[u] = *reinterpret_cast<const float2 *>(v0 + u * rs);
+        for (int u = 0; u < 8; ++u)
+            x[u] = *reinterpret_cast<const float2 *>(MODE == 2 ? vp + (long long)rw[j + u * DEC_WAVES] * hd : v0 + u * rs);
         float pj[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) pj[u] = ps[j + u * DEC_WAVES];
@@ -690,7 +711,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void lvt_attn_decode_kernel(const f
     }
     for (; j < nk; j += DEC_WAVES) {
         const float p = ps[j];
-        const float2 x = *reinterpret_cast<const float2 *>(vp + (long long)j * hd);
+        const float2 x = *reinterpret_cast<const float2 *>(vp + (long long)(MODE == 2 ? rw[j] : j) * hd);
         a0 = fmaf(p, x.x, a0);
         a1 = fmaf(p, x.y, a1);
     }
@@ -699,6 +720,26 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void lvt_attn_decode_kernel(const f
     __syncthreads();
     if (tid < DEC_DA)
         o[(long long)b * hd + h * DEC_DA + tid] = (((acc[0][tid] + acc[1][tid]) + acc[2][tid]) + acc[3][tid]) / sum;
+}
+__global__ __launch_bounds__(64 * DEC_WAVES) void lvt_attn_decode_kernel(const float *__restrict__ q, long long ldq,
+                                                             const float *__restrict__ Kc,
+                                                             const float *__restrict__ Vc, int H, int S, int qi,
+                                                             float temper, const float *__restrict__ dt,
+                                                             const float *__restrict__ dh, const float *__restrict__ dw,
+                                                             BiasGeom g, float *__restrict__ o,
+                                                             const int *__restrict__ pos, long long q_pos) {
+    attn_decode_body<0>(q, ldq, Kc, Vc, H, S, qi, temper, dt, dh, dw, g, g, o, pos, q_pos);
+}
+template <int MODE>
+__global__ __launch_bounds__(64 * DEC_WAVES) void lvt_attn_decode_blocks_kernel(const float *__restrict__ q, long long ldq,
+                                                                    const float *__restrict__ Kc,
+                                                                    const float *__restrict__ Vc, int H, int S, int qi,
+                                                                    float temper, const float *__restrict__ dt,
+                                                                    const float *__restrict__ dh,
+                                                                    const float *__restrict__ dw, BiasGeom g, BiasGeom vol,
+                                                                    float *__restrict__ o, const int *__restrict__ pos,
+                                                                    long long q_pos) {
+    attn_decode_body<MODE>(q, ldq, Kc, Vc, H, S, qi, temper, dt, dh, dw, g, vol, o, pos, q_pos);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -782,6 +823,29 @@ extern "C" int lvt_attn_decode(const float *q, long long ldq, const float *Kc, c
     hipLaunchKernelGGL(lvt_attn_decode_kernel, dim3(B * H), dim3(64 * DEC_WAVES), 0, (hipStream_t)stream, q, ldq, Kc, Vc, H, S, qi,
                        temper, dt, dh, dw, g, o, pos, q_pos);
     LVT_CHECK_LAUNCH("lvt_attn_decode_kernel");
+    return LVT_OK;
+}
+
+extern "C" int lvt_attn_decode_blocks(const float *q, long long ldq, const float *Kc, const float *Vc, int B, int H, int da, int qi,
+                                      float temper, const float *dt, const float *dh, const float *dw, int st, int sh, int sw,
+                                      int bt, int bh, int bw, float *o, const int *pos, long long q_pos, void *stream) {
+    LVT_REQUIRE(q && Kc && Vc && dt && dh && dw && o && B > 0 && H > 0, "attn_decode_blocks: bad args");
+    LVT_REQUIRE(da == DEC_DA, "attn_decode_blocks: da=%d (only %d is instantiated)", da, DEC_DA);
+    LVT_REQUIRE(st > 0 && sh > 0 && sw > 0 && bt > 0 && bh > 0 && bw > 0 && st % bt == 0 && sh % bh == 0 && sw % bw == 0,
+                "attn_decode_blocks: slice (%d,%d,%d) is not a multiple of the block (%d,%d,%d)", st, sh, sw, bt, bh, bw);
+    LVT_REQUIRE((long long)bt * bh * bw <= DEC_MAXKEYS, "attn_decode_blocks: block of %lld keys (max %d)", (long long)bt * bh * bw,
+                DEC_MAXKEYS);
+    const long long S = (long long)st * sh * sw;
+    LVT_REQUIRE(S <= 0x7fffffffLL && qi >= 0 && qi < S, "attn_decode_blocks: slice of %lld tokens / qi=%d", S, qi);
+    LVT_REQUIRE(ldq >= (long long)H * da, "attn_decode_blocks: ldq");
+    BiasGeom g = {bt, bh, bw}, vol = {st, sh, sw};
+    if (bh == sh && bw == sw)
+        hipLaunchKernelGGL(lvt_attn_decode_blocks_kernel<1>, dim3(B * H), dim3(64 * DEC_WAVES), 0, (hipStream_t)stream, q, ldq, Kc,
+                           Vc, H, (int)S, qi, temper, dt, dh, dw, g, vol, o, pos, q_pos);
+    else
+        hipLaunchKernelGGL(lvt_attn_decode_blocks_kernel<2>, dim3(B * H), dim3(64 * DEC_WAVES), 0, (hipStream_t)stream, q, ldq, Kc,
+                           Vc, H, (int)S, qi, temper, dt, dh, dw, g, vol, o, pos, q_pos);
+    LVT_CHECK_LAUNCH("lvt_attn_decode_blocks_kernel");
     return LVT_OK;
 }
 

@@ -252,6 +252,21 @@ def attn_decode(q, Kc, Vc, H, qi, temper, dt, dh, dw, block, ldq=None, pos=None,
     return o
 
 
+def attn_decode_blocks(q, Kc, Vc, H, qi, temper, dt, dh, dw, thw, block, ldq=None, pos=None, q_pos=0):
+    """attn_decode for a slice `thw` whose attention runs inside blocks `block` (each extent divides the slice's): the
+    caches stay (B, S, H*da) in slice raster order, S = t*h*w, and the query at slice position qi attends the keys of its
+    own block up to itself.  ldq / pos / q_pos as for attn_decode."""
+    L.require(Kc, Vc, dt, dh, dw, pos)
+    B, S, hd = Kc.shape
+    if S != thw[0] * thw[1] * thw[2]:
+        raise L.LvtError("attn_decode_blocks: caches of %d rows for a slice %s" % (S, tuple(thw)))
+    o = torch.empty(B, hd, dtype=torch.float32, device=Kc.device)
+    L.check(L.lib().lvt_attn_decode_blocks(C.c_void_p(q.data_ptr()), ldq if ldq is not None else hd, L.ptr(Kc), L.ptr(Vc), B, H, hd // H, qi,
+                                           temper, L.ptr(dt), L.ptr(dh), L.ptr(dw), thw[0], thw[1], thw[2], block[0], block[1],
+                                           block[2], L.ptr(o), L.ptr(pos), q_pos, L.stream_ptr()), "lvt_attn_decode_blocks")
+    return o
+
+
 def sample_categorical(logits, temp, u, out, out_stride=1, want_probs=False, pos=None, u_pos=0):
     """Draw one code per row of `logits` (rows, V) with the uniforms `u` (rows,); the int64 codes go to
     out.data_ptr() + row * out_stride (elements).  Returns the probabilities when asked for.

@@ -7,6 +7,11 @@ depends only on tokens < i, so token i can be computed alone against cached keys
 tokens: S single-token steps per slice, the same arithmetic per row (the masked columns of the full pass
 carry exactly zero probability).  `tests/test_gpu_sampling.py` checks step(i) against row i of the full pass.
 
+A layer whose attention block is smaller than the slice (block-split attention, vt_attention.py:189-200; DSSVT sampled at
+16 frames) is causal inside each block in the block's own raster order, which is the slice's raster order restricted to
+the block: token i still depends only on tokens < i.  Its keys are the tokens of i's block at or before i; the caches stay
+in slice order and `tx.attn_decode_blocks` finds the block's rows (`tests/test_gpu_sampling_blocksplit.py`).
+
 The position being decoded lives in DEVICE memory (`IncrementalDecoder.pos`, one int32): every kernel of a step
 that addresses by position (neighbour gather, the row of the K/V caches written by the q/k/v product, the residual
 row of the front end, the number of keys of the decode attention, the write-back of the drawn codes) reads it
@@ -27,7 +32,27 @@ from ...hip import gemm as G
 
 
 class IncrementalDecoder:
+    @staticmethod
+    def supports(decoder, thw):
+        """Host-side check: can a slice of `thw` tokens be decoded against K/V caches?  Every layer's block must divide
+        the slice (as the training path requires) and hold at most 1024 keys (the decode attention's bound), da == 128."""
+        return all(len(thw) == 3 and all(s > 0 and s % k == 0 for s, k in zip(thw, l.block_size))
+                   and l.block_size[0] * l.block_size[1] * l.block_size[2] <= 1024 and l.mha.da == 128
+                   for l in decoder.block_local_attention)
+
+    @staticmethod
+    def bytes_per_video(decoder, thw):
+        """Device memory one video of a decode group holds for a slice of `thw`: per layer the (3, S, hd) query / key / value
+        rows, plus the (S, d) front-end base (the other per-video buffers are a few rows)."""
+        S = thw[0] * thw[1] * thw[2]
+        return 4 * S * (sum(3 * l.mha.na * l.mha.da for l in decoder.block_local_attention)
+                        + decoder.linear_projector.weight.shape[0])
+
     def __init__(self, decoder, zl_tok, b, thw):
+        thw = tuple(thw)
+        if not self.supports(decoder, thw):
+            raise L.LvtError("IncrementalDecoder: slice %s is not a multiple of every layer's attention block %s (at most "
+                             "1024 tokens per block, da == 128)" % (thw, [tuple(l.block_size) for l in decoder.block_local_attention]))
         t, h, w = thw
         self.dec, self.b, self.thw, self.S = decoder, b, thw, t * h * w
         dev = zl_tok.device
@@ -96,7 +121,7 @@ class IncrementalDecoder:
     def begin_slice(self, zl_tok):
         """position signal + projection of the encoder output: fixed for the whole slice (written in place so
         that captured graphs keep seeing the same buffer).  Stale cache rows need no reset: step(i) only reads
-        keys 0..i, all of which are rewritten while the new slice is decoded."""
+        keys at or before i (of i's block), all of which are rewritten while the new slice is decoded."""
         t, h, w = self.thw
         self._refresh_weights()
         G.gemm(zl_tok, self.dec.linear_projector.weight, self.base, self.b * self.S, self.d, self.d)
@@ -165,8 +190,12 @@ class IncrementalDecoder:
             qkv = self.qkv[li]
             G.gemm_small(xn, self.wqkv[li], qkv, b, hd, d, ldc=S * hd, batch=3, sB=hd * d, sC=b * S * hd,
                          split_ws=self._split_ws, pos=self.pos, c_pos=hd)
-            o = tx.attn_decode(qkv, self.kc[li], self.vc[li], na, 0, math.sqrt(da), layer.dt_bank,
-                               layer.dh_bank, layer.dw_bank, layer.block_size, ldq=S * hd, pos=self.pos, q_pos=hd)
+            if tuple(layer.block_size) == self.thw:
+                o = tx.attn_decode(qkv, self.kc[li], self.vc[li], na, 0, math.sqrt(da), layer.dt_bank,
+                                   layer.dh_bank, layer.dw_bank, layer.block_size, ldq=S * hd, pos=self.pos, q_pos=hd)
+            else:
+                o = tx.attn_decode_blocks(qkv, self.kc[li], self.vc[li], na, 0, math.sqrt(da), layer.dt_bank, layer.dh_bank,
+                                          layer.dw_bank, self.thw, layer.block_size, ldq=S * hd, pos=self.pos, q_pos=hd)
             if hd % KS == 0 and d % 4 == 0:
                 ws = G.gemm_small_partial(o, m.proj.weight, b, d, hd, hd // KS, self._partials("proj", hd // KS))
                 y1, fn = G.splitsum_layernorm(ws, hd // KS, b, d, f[0].weight, f[0].bias, res=x)

@@ -46,11 +46,30 @@ class _XentFn(torch.autograd.Function):
 DECODE_GROUP_STREAMS = os.environ.get("LVT_DECODE_GROUP_STREAMS", "1") != "0"      # "0": groups one after the other
 MAX_CONCURRENT_GROUPS = 3
 DECODE_GROUP_ROWS = 256          # videos per decode group (rows of every decode-step launch)
+# A group owns the K/V caches of its videos: IncrementalDecoder.bytes_per_video, 3 * S * hd * 4 bytes per layer -- 25 MB per
+# video for a 256-token slice of the shipped 8-layer decoders, 100 MB for the 1024-token slices of DSSVT at 16 frames (77 GB for
+# three concurrent groups of 256).  Rule: the groups that run concurrently may hold at most DECODE_MEMORY_FRACTION of the
+# device memory that is free when the samplers are built; a long slice on a busy or smaller device therefore lowers the rows
+# per group (decode_group_rows), and a batch of more than MAX_CONCURRENT_GROUPS such groups is sampled in successive passes.
+DECODE_MEMORY_FRACTION = 0.5
 # The host issues a decode step (one graph launch per group) ~50x faster than the GPU executes it and nothing in the
 # sampling loop needs a result on the host, so unchecked it would queue every step of every remaining slice (thousands of
 # graph launches, ~10^6 AQL packets across streams that wait on each other) ahead of the device.  The loop therefore never
 # runs more than this many positions ahead of the slowest group (event per window, host waits on the window before last).
 DECODE_MAX_STEPS_AHEAD = int(os.environ.get("LVT_DECODE_MAX_STEPS_AHEAD", "64"))
+
+
+def decode_group_rows(bytes_per_video, free_bytes):
+    """Videos per decode group: DECODE_GROUP_ROWS, or fewer when MAX_CONCURRENT_GROUPS such groups would not fit into
+    DECODE_MEMORY_FRACTION of `free_bytes` (the rule next to DECODE_GROUP_ROWS); never less than one."""
+    fit = int(DECODE_MEMORY_FRACTION * free_bytes) // (MAX_CONCURRENT_GROUPS * bytes_per_video)
+    return max(1, min(DECODE_GROUP_ROWS, fit))
+
+
+def _free_device_bytes(device):
+    """Memory a new allocation can draw on: what the driver reports free plus what torch's allocator holds unused."""
+    free, _ = torch.cuda.mem_get_info(device)
+    return free + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
 
 
 class _RunAhead:
@@ -208,10 +227,11 @@ class VideoTransformerModel(nn.Module):
         """video (B, nc, T, H, W) int64 with the first n_prime frames given; returns the completed grid.
 
         incremental=True (default): encoder once per slice, then ONE single-token decoder step per position
-        against K/V caches (modeling/autoregressive/incremental.py).  incremental=False reproduces the
-        reference's schedule (full decoder pass per generated pixel, vt.py:121-131); both draw from the same
-        per-pixel distributions."""
-        from ..autoregressive.incremental import GraphedSliceSampler
+        against K/V caches (modeling/autoregressive/incremental.py), for every slice that is a multiple of each
+        decoder layer's attention block (block-split layers included: DSSVT at 16 frames).  incremental=False
+        reproduces the reference's schedule (full decoder pass per generated pixel, vt.py:121-131); both draw from
+        the same per-pixel distributions."""
+        from ..autoregressive.incremental import GraphedSliceSampler, IncrementalDecoder
         self._require_gpu()
         v = self._vt
         video = video.to(self.device).clone()
@@ -224,9 +244,9 @@ class VideoTransformerModel(nn.Module):
             prime[:n_prime] = True
         pred = self.model.ch_predictor
         sampler = None
-        # the K/V-cache decoder attends over the whole slice; block-split layers (slice larger than the attention
-        # block, e.g. DSSVT at 16 frames) fall back to the reference schedule
-        if any(tuple(l.block_size) != (t, h, w) for l in self.model.decoder.block_local_attention):
+        # a slice that no K/V-cache decoder can be built for (not a multiple of a layer's block) keeps the reference schedule,
+        # which raises where the training path does
+        if not IncrementalDecoder.supports(self.model.decoder, (t, h, w)):
             incremental = False
         groups = None
         if incremental:
@@ -235,11 +255,18 @@ class VideoTransformerModel(nn.Module):
             # group of 256 videos is 4x the workgroups at almost the same step time), and independent groups on separate
             # streams (own K/V caches and graphs) whose steps interleave on the GPU.  Measured on 1 MI355X, frames/s:
             # 527 (64 videos), 932 (128), 1341 (256), 1696 (512) in one group; 1956 for 3 groups of 256.
-            ng = (B + DECODE_GROUP_ROWS - 1) // DECODE_GROUP_ROWS
-            bounds = [B * g // ng for g in range(ng + 1)]
             key = (B, t, h, w, float(temp))
             groups = self._samplers.get(key) if hasattr(self, "_samplers") else None
             if groups is None:
+                rows = decode_group_rows(IncrementalDecoder.bytes_per_video(self.model.decoder, (t, h, w)),
+                                         _free_device_bytes(video.device))
+                if rows < DECODE_GROUP_ROWS and B > MAX_CONCURRENT_GROUPS * rows:   # memory-bound: one wave of groups per pass
+                    n = MAX_CONCURRENT_GROUPS * rows
+                    return torch.cat([self.sample_video(video[i:i + n], temp, n_prime,
+                                                        None if class_idx is None else class_idx[i:i + n])
+                                      for i in range(0, B, n)])
+                ng = (B + rows - 1) // rows
+                bounds = [B * g // ng for g in range(ng + 1)]
                 groups = [(bounds[g], bounds[g + 1], GraphedSliceSampler(self.model, bounds[g + 1] - bounds[g], (t, h, w), temp),
                            (torch.cuda.Stream(device=video.device) if DECODE_GROUP_STREAMS else
                             torch.cuda.current_stream(video.device)) if ng > 1 else None) for g in range(ng)]
