@@ -33,7 +33,7 @@ extern "C" {
 #define LVT_ENODEVICE   (-4)   /* no gfx950 device visible                             */
 
 const char *lvt_last_error(void);
-int lvt_version(void);          /* 640 = block-local decode attention (ABI changes are listed in INTEGRATION.md) */
+int lvt_version(void);          /* 650 = sigmoid output activation (ABI changes are listed in INTEGRATION.md) */
 /* Device probe: name, CU count, clock (kHz), HBM bytes.  Returns LVT_ENODEVICE without a GPU. */
 int lvt_device_info(char *name, int name_len, int *cus, int *clock_khz, long long *hbm_bytes);
 
@@ -98,6 +98,14 @@ int lvt_amax_merge(const float *a, const float *b, float *out, void *stream);
                                  * (v = p1 + p2 + p3, round-to-nearest-even at every level): plane j of element (m, n) at
                                  * ((uint16_t *)C)[j*c_plane + z-offset + m*ldc + n]; ldc, sC_*, c_plane count bf16 elements.
                                  * The operand format of lvt_attn_fwd_planes / lvt_attn_bwd_planes.                          */
+#define LVT_EPI_SIGMOID   128   /* 1 / (1 + e^-x) (ABI 650): accepted wherever LVT_EPI_TANH is (the conv entry points, lvt_bn_apply);
+                                 * the last activation of a layer, after bias and residual, like TANH.  Absolute error below
+                                 * 2^-22; exactly 0 for inputs below -88.7, exactly 1 above 16.7, never NaN for a finite input. */
+/* With LVT_EPI_SIGMOID: the last n (0..3) output channels are the zero pads of a channel count carried as a multiple of 4 and
+ * are stored as 0 instead of sigmoid(0) = 0.5, so the pad channels of every activation stay 0 (tanh and ReLU keep them by
+ * themselves).  Ignored without LVT_EPI_SIGMOID.                                                                            */
+#define LVT_EPI_PAD(n)    (((n) & 3) << 24)
+#define LVT_EPI_PAD_OF(flags) (((flags) >> 24) & 3)
 /* causal structure of the batched attention products of a masked layer (M, N, K token positions of one block):          */
 #define LVT_CAUSAL_KMAX   (1 << 8)    /* A(m,k) == 0 for k > m: a tile reduces over k < m0 + 128 only  (dQ = dS K)        */
 #define LVT_CAUSAL_KMIN   (1 << 9)    /* A(m,k) == 0 for k < m: a tile starts its reduction at k = m0  (dV = P^T dO, dK)  */
@@ -266,7 +274,7 @@ int lvt_conv3d_pack_weight_parity(const lvt_conv_geom *g, const float *w, int Ci
 int lvt_conv3d_fwd_parity(const lvt_conv_geom *g, const float *x, const float *wq, const float *bias,
                           const float *res, const float *mask, float *y, int flags, const lvt_amax_io *ax,
         void *stream);
-/* y = epi( conv(x, wp) ); bias[Co]; res / y are (N,To,Ho,Wo,Co).  flags: BIAS|RESIDUAL|RELU|TANH|MASK */
+/* y = epi( conv(x, wp) ); bias[Co]; res / y are (N,To,Ho,Wo,Co).  flags: BIAS|RESIDUAL|RELU|TANH|SIGMOID (+ PAD(n))|MASK */
 int lvt_conv3d_fwd(const lvt_conv_geom *g, const float *x, const float *wp, const float *bias,
                    const float *res, const float *mask, float *y, int flags, const lvt_amax_io *ax,
         void *stream);
@@ -280,7 +288,7 @@ int lvt_conv3d_bwd_data_phases(const lvt_conv_geom *g, const float *dy, const fl
                                const float *res, const float *mask, float *dx, int flags, const lvt_amax_io *ax,
         void *stream);
 /* dx = epi( conv_transpose(dy, wp) ); res / mask / dx are (N,Ti,Hi,Wi,Ci).
- * flags: BIAS (bias[Ci], used when this IS a ConvTranspose forward) | RESIDUAL | RELU | TANH | MASK.
+ * flags: BIAS (bias[Ci], used when this IS a ConvTranspose forward) | RESIDUAL | RELU | TANH | SIGMOID (+ PAD(n)) | MASK.
  * Requires Kt % st == 0 etc. and To*st == Ti-ish geometries produced by lvt_conv geometry helpers.  */
 int lvt_conv3d_bwd_data(const lvt_conv_geom *g, const float *dy, const float *wp, const float *bias,
                         const float *res, const float *mask, float *dx, int flags, const lvt_amax_io *ax,
@@ -313,6 +321,10 @@ int lvt_conv3d_bwd_weight(const lvt_conv_geom *g, const float *x, const float *d
  * the 3 x 3 neighbours x Ci on v_mfma_f32_16x16x32_f16, persistent workgroups, weights split once per workgroup.          */
 int lvt_convt4_fwd(const float *x, const float *w, const float *bias, int N, int Hi, int Wi, int Ci, int Cr,
                    int act_tanh, float *y, int flags, const lvt_amax_io *ax, void *stream);
+/* The same layer with an activation CODE (ABI 650): act = 0, LVT_EPI_TANH or LVT_EPI_SIGMOID.  lvt_convt4_fwd(.., act_tanh, ..)
+ * is this call with act = act_tanh ? LVT_EPI_TANH : 0.  Channels Cr..3 of y are 0 under every activation.                   */
+int lvt_convt4_fwd_act(const float *x, const float *w, const float *bias, int N, int Hi, int Wi, int Ci, int Cr,
+                       int act, float *y, int flags, const lvt_amax_io *ax, void *stream);
 /* out[n] (+)= sum_m g[m*ld + n]  (bias gradients).  workspace >= lvt_colsum_workspace_bytes.        */
 size_t lvt_colsum_workspace_bytes(long long M, int N);
 int lvt_colsum(const float *g, long long M, int N, long long ld, float *out, void *workspace,
@@ -383,6 +395,8 @@ int lvt_l1_fwd(const float *a, const float *b, long long n, double denom, float 
 int lvt_l1_bwd(const float *a, const float *b, long long n, double denom, float scale,
                const float *gout_dev, const float *add, int tanh_of_a, float *out, float *out_amax, void *stream);
 int lvt_tanh_bwd(const float *g, const float *y, long long n, float *out, float *out_amax, void *stream);
+/* out = g * y * (1 - y), y the saved sigmoid output (ABI 650); out_amax as on lvt_tanh_bwd                */
+int lvt_sigmoid_bwd(const float *g, const float *y, long long n, float *out, float *out_amax, void *stream);
 /* out = alpha * alpha_dev[0] * x (+ add)                                                              */
 int lvt_axpy(const float *x, const float *add, long long n, const float *alpha_dev, float alpha,
              float *out, void *stream);
@@ -599,7 +613,8 @@ int lvt_bn_stats(const float *y, long long M, int Cp, float *stats, void *worksp
 int lvt_bn_finalize(const float *stats, int nranks, long long count, int C, int Cp, const float *gamma, const float *beta,
                     float *running_mean, float *running_var, long long *num_batches_tracked, float momentum, float eps,
                     int flags, float *scale, float *shift, float *saved, void *stream);
-/* out = act(y * scale[c] + shift[c] (+ res)), act = LVT_EPI_RELU / LVT_EPI_TANH / none (flags); res nullable.
+/* out = act(y * scale[c] + shift[c] (+ res)), act = LVT_EPI_RELU / LVT_EPI_TANH / LVT_EPI_SIGMOID / none (flags); res nullable.
+ * With LVT_EPI_SIGMOID | LVT_EPI_PAD(n) the last n channels of every row are stored as 0 (ABI 650).
  * out_amax (nullable): max |out| folded in as by the engine's c_amax.                                                    */
 int lvt_bn_apply(const float *y, const float *res, long long M, int Cp, const float *scale, const float *shift, int flags,
                  float *out, float *out_amax, void *stream);

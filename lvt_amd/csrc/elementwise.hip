@@ -241,6 +241,29 @@ extern "C" int lvt_tanh_bwd(const float *g, const float *y, long long n, float *
     return LVT_OK;
 }
 
+// out = g * y * (1 - y)   (sigmoid backward at the end of a conv stack, from the saved output)
+__global__ void lvt_sigmoid_bwd_kernel(const float *__restrict__ g, const float *__restrict__ y, long long n4,
+                                       float *__restrict__ out, float *__restrict__ out_amax) {
+    __shared__ float amax_scratch[4];
+    float am = 0.f;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
+         i += (long long)gridDim.x * blockDim.x) {
+        const float4 a = reinterpret_cast<const float4 *>(g)[i];
+        const float4 t = reinterpret_cast<const float4 *>(y)[i];
+        const float4 r = make_float4(a.x * (t.x * (1.f - t.x)), a.y * (t.y * (1.f - t.y)), a.z * (t.z * (1.f - t.z)), a.w * (t.w * (1.f - t.w)));
+        reinterpret_cast<float4 *>(out)[i] = r;
+        am = fmaxf(am, fmaxf(fmaxf(lvt_absf(r.x), lvt_absf(r.y)), fmaxf(lvt_absf(r.z), lvt_absf(r.w))));
+    }
+    if (out_amax) lvt_block_amax_commit(am, out_amax, amax_scratch);
+}
+extern "C" int lvt_sigmoid_bwd(const float *g, const float *y, long long n, float *out, float *out_amax, void *stream) {
+    LVT_REQUIRE(g && y && out && n > 0 && n % 4 == 0, "sigmoid_bwd: bad args");
+    hipLaunchKernelGGL(lvt_sigmoid_bwd_kernel, dim3(grid_for(n / 4, 256, out_amax ? 2048 : 8192)), dim3(256), 0, (hipStream_t)stream, g, y,
+                       n / 4, out, out_amax);
+    LVT_CHECK_LAUNCH("lvt_sigmoid_bwd_kernel");
+    return LVT_OK;
+}
+
 // x[r][:] += table[r % P][:]   (positional encoding, vt_attention.py:25-50)
 __global__ void lvt_add_periodic_kernel(float *__restrict__ x, const float *__restrict__ table, long long rows,
                                         int P, int d4) {

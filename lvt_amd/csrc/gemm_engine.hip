@@ -721,7 +721,7 @@ struct PatchRows { __device__ __forceinline__ long long operator()(int row) cons
 struct PatchTRows { int cls; __device__ __forceinline__ long long operator()(int row) const { return patcht_orow(row, cls); } };
 
 // ------------------------------------------------------------------------------------------------
-// epilogue shared by the kernels: alpha / bias / residual / ReLU / tanh / mask / accumulate, or split-K partials
+// epilogue shared by the kernels: alpha / bias / residual / ReLU / tanh / sigmoid / mask / accumulate, or split-K partials
 // ------------------------------------------------------------------------------------------------
 template <int AMODE, int BM, int BN, int WM, int WN>
 __device__ __forceinline__ void lvt_epilogue(const KParams &p, f32x16 (&acc)[BM / WM / 32][BN / WN / 32], int m0, int n0,
@@ -771,6 +771,7 @@ __device__ __forceinline__ void lvt_epilogue(const KParams &p, f32x16 (&acc)[BM 
                 if (flags & LVT_EPI_RESIDUAL) v += p.res[coff + orow * p.ldr + col];
                 if (flags & LVT_EPI_RELU) v = fmaxf(v, 0.f);
                 if (flags & LVT_EPI_TANH) v = tanhf(v);
+                if (flags & LVT_EPI_SIGMOID) v = lvt_sigmoid_col(v, col < p.N - LVT_EPI_PAD_OF(flags));
                 if (flags & LVT_EPI_MASK) v = (p.mask[coff + orow * p.ldm + col] > 0.f) ? v : 0.f;
                 float *cp = p.C + coff + orow * p.ldc + col;
                 if (flags & LVT_EPI_ACCUM) v += *cp;
@@ -925,6 +926,10 @@ __device__ __forceinline__ void lvt_epilogue_vec(const KParams &p, f32x16 (&acc)
                     v.x += rv[u].x; v.y += rv[u].y; v.z += rv[u].z; v.w += rv[u].w;
                     if (flags & LVT_EPI_RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
                     if (flags & LVT_EPI_TANH) { v.x = tanhf(v.x); v.y = tanhf(v.y); v.z = tanhf(v.z); v.w = tanhf(v.w); }
+                    if (flags & LVT_EPI_SIGMOID) {          // (N is a multiple of 4: the pads are the tail of the last float4)
+                        const int nr = p.N - LVT_EPI_PAD_OF(flags) - col;
+                        v.x = lvt_sigmoid_col(v.x, nr > 0); v.y = lvt_sigmoid_col(v.y, nr > 1); v.z = lvt_sigmoid_col(v.z, nr > 2); v.w = lvt_sigmoid_col(v.w, nr > 3);
+                    }
                     v.x = mv[u].x > 0.f ? v.x : 0.f; v.y = mv[u].y > 0.f ? v.y : 0.f; v.z = mv[u].z > 0.f ? v.z : 0.f; v.w = mv[u].w > 0.f ? v.w : 0.f;
                     am = fmaxf(am, fmaxf(fmaxf(lvt_absf(v.x), lvt_absf(v.y)), fmaxf(lvt_absf(v.z), lvt_absf(v.w))));
                     *reinterpret_cast<float4 *>(p.C + coff + orow * p.ldc + col) = v;
@@ -958,6 +963,10 @@ __device__ __forceinline__ void lvt_epilogue_vec(const KParams &p, f32x16 (&acc)
                         if (flags & LVT_EPI_RESIDUAL) { const float4 b = ldg4(p.res + coff + orow * p.ldr + col); v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w; }
                         if (flags & LVT_EPI_RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
                         if (flags & LVT_EPI_TANH) { v.x = tanhf(v.x); v.y = tanhf(v.y); v.z = tanhf(v.z); v.w = tanhf(v.w); }
+                        if (flags & LVT_EPI_SIGMOID) {          // (N is a multiple of 4: the pads are the tail of the last float4)
+                            const int nr = p.N - LVT_EPI_PAD_OF(flags) - col;
+                            v.x = lvt_sigmoid_col(v.x, nr > 0); v.y = lvt_sigmoid_col(v.y, nr > 1); v.z = lvt_sigmoid_col(v.z, nr > 2); v.w = lvt_sigmoid_col(v.w, nr > 3);
+                        }
                         if (flags & LVT_EPI_MASK) {
                             const float4 mk = ldg4(p.mask + coff + orow * p.ldm + col);
                             v.x = mk.x > 0.f ? v.x : 0.f; v.y = mk.y > 0.f ? v.y : 0.f; v.z = mk.z > 0.f ? v.z : 0.f; v.w = mk.w > 0.f ? v.w : 0.f;
@@ -1169,7 +1178,7 @@ __global__ __launch_bounds__(NTHREADS, (MATH == 2 ? 2 : 1)) void lvt_gemm_kernel
         if (al.sum_on) al.write_colsum(lds, p.colsum_partial + ((long long)split * gridDim.y + z) * p.M, m0, p.M, tid);
     }
     if constexpr (AMODE != A_CONVT_K && TM == 2 && TN == 2 && LDS_FLOATS >= TURN_FLOATS + 16) {
-        if (p.vec_epi && !(p.flags & (LVT_EPI_PLANES | LVT_EPI_ACCUM | LVT_EPI_TANH))) {
+        if (p.vec_epi && !(p.flags & (LVT_EPI_PLANES | LVT_EPI_ACCUM | LVT_EPI_TANH | LVT_EPI_SIGMOID))) {
             // every form whose tile rows ARE the rows of C: epilogue_fast.h (same arithmetic, see there)
             LvtEpi e;
             e.M = p.M; e.N = p.N;
@@ -1458,7 +1467,7 @@ __global__ __launch_bounds__(PT_THREADS) void lvt_conv_patch_kernel(const KParam
         __syncthreads();
     }
     if constexpr (MATH == 2) lvt_f16x2_finish<TM, TN>(acc, acx, unscale);
-    if (p.vec_epi && p.splits <= 1 && !(p.flags & (LVT_EPI_PLANES | LVT_EPI_ACCUM | LVT_EPI_TANH))) {
+    if (p.vec_epi && p.splits <= 1 && !(p.flags & (LVT_EPI_PLANES | LVT_EPI_ACCUM | LVT_EPI_TANH | LVT_EPI_SIGMOID))) {
         // epilogue_fast.h with the pixel permutation of the frame as its row map
         const unsigned seen = lvt_amax_peek(p.c_amax);
         LvtEpi e;
@@ -1685,7 +1694,7 @@ __global__ __launch_bounds__(WIDE_THREADS, 2) void lvt_gemm_wide_kernel(const KP
         }
         __syncthreads();
     }
-    if (p.vec_epi && !(p.flags & (LVT_EPI_PLANES | LVT_EPI_ACCUM | LVT_EPI_TANH))) {
+    if (p.vec_epi && !(p.flags & (LVT_EPI_PLANES | LVT_EPI_ACCUM | LVT_EPI_TANH | LVT_EPI_SIGMOID))) {
         // plain forms (every launch of the transformer): epilogue_fast.h -- same arithmetic, compile-time flag sets, no workgroup
         // barriers, max |C| peeked before the stores
         LvtEpi e;

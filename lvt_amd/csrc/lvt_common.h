@@ -44,6 +44,16 @@ __device__ __forceinline__ float lvt_absf(float a) {
     const float b = fabsf(a);
     return b < __builtin_inff() ? b : 0.f;
 }
+// LVT_EPI_SIGMOID: 1 / (1 + 2^(-v log2 e)) on v_exp_f32 and v_rcp_f32 (1 ulp each), four instructions and no temporaries per
+// element -- libm's expf and the IEEE quotient cost the 128 x 128 transposed-convolution tile kernel 24 registers and with them
+// its second wave per SIMD.  The rounding of the exponent's argument is a relative error |v| 2^-23.5 of e^-v, which
+// the quotient damps by e^-v / (1 + e^-v)^2: the absolute error stays below 2^-22 for every v.  2^x overflows to +inf below
+// v = -88.7 and the reciprocal is then exactly 0; above v = 16.7 the sum rounds to 1.  No NaN for a finite v.
+// `real`: the column is a channel of the layer, not one of the zero pads (LVT_EPI_PAD), which stay 0 instead of sigmoid(0).
+__device__ __forceinline__ float lvt_sigmoidf(float v) {
+    return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(v * -1.44269504088896341f));
+}
+__device__ __forceinline__ float lvt_sigmoid_col(float v, bool real) { return real ? lvt_sigmoidf(v) : 0.f; }
 __device__ __forceinline__ void lvt_block_amax_commit(float m, float *dst, float *scratch) {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));

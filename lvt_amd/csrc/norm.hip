@@ -222,9 +222,11 @@ __global__ void lvt_bn_finalize_kernel(const float *__restrict__ stats, int nran
     }
 }
 
-__device__ __forceinline__ float bn_act(float v, int flags) {
+// real: the channel is not one of the zero pads (only the sigmoid, whose value at 0 is not 0, needs to know)
+__device__ __forceinline__ float bn_act(float v, int flags, bool real) {
     if (flags & LVT_EPI_RELU) return fmaxf(v, 0.f);
     if (flags & LVT_EPI_TANH) return tanhf(v);
+    if (flags & LVT_EPI_SIGMOID) return lvt_sigmoid_col(v, real);
     return v;
 }
 
@@ -244,7 +246,8 @@ __global__ __launch_bounds__(BN_THREADS) void lvt_bn_apply_kernel(const float *_
             const float4 e = ld4(res + i * 4);
             r.x += e.x; r.y += e.y; r.z += e.z; r.w += e.w;
         }
-        r.x = bn_act(r.x, flags); r.y = bn_act(r.y, flags); r.z = bn_act(r.z, flags); r.w = bn_act(r.w, flags);
+        const int nr = Cp - LVT_EPI_PAD_OF(flags) - c;
+        r.x = bn_act(r.x, flags, nr > 0); r.y = bn_act(r.y, flags, nr > 1); r.z = bn_act(r.z, flags, nr > 2); r.w = bn_act(r.w, flags, nr > 3);
         st4(out + i * 4, r);
         m = fmaxf(m, fmaxf(fmaxf(lvt_absf(r.x), lvt_absf(r.y)), fmaxf(lvt_absf(r.z), lvt_absf(r.w))));
     }

@@ -7,7 +7,8 @@
 
 // ------------------------------------------------------------------------------------------------
 // y[n, 2q+r, :, c] = act( bias[c] + sum_{ci, taps} x[n, q+d, :, ci] * W[ci][c][kh][kw] ),  k4 s2 p1 ConvTranspose
-// x (N, Hi, Wi, Ci) channels-last, y (N, 2Hi, 2Wi, 4) with channel 3 == act(0) padding, W in torch
+// x (N, Hi, Wi, Ci) channels-last, y (N, 2Hi, 2Wi, 4) with channels Cr..3 == 0 padding (act: 0 / LVT_EPI_TANH / LVT_EPI_SIGMOID;
+// the pads are not activated: sigmoid(0) is not 0), W in torch
 // ConvTranspose2d layout (Ci, Cr, 4, 4) with Cr <= 3.
 // A thread owns the 2x2 output blocks of TC_P input positions; a workgroup owns a 16 x 32 input tile (+1 halo) and
 // walks Ci in chunks of 16 staged through LDS.  Every kernel tap k (per dimension) belongs to exactly one
@@ -28,7 +29,7 @@ __device__ __forceinline__ float tc_comp(const float4 &v, int j) { return j == 0
 
 __global__ __launch_bounds__(256) void lvt_convt4_fwd_kernel(const float *__restrict__ x, const float *__restrict__ w,
                                                              const float *__restrict__ bias, int N, int Hi, int Wi,
-                                                             int Ci, int Cr, int act_tanh, float *__restrict__ y) {
+                                                             int Ci, int Cr, int act, float *__restrict__ y) {
     __shared__ __attribute__((aligned(16))) float xs[(TC_TH + 2) * (TC_TW + 2) * TC_LDX];
     const int tid = threadIdx.x;
     const int tiles_w = (Wi + TC_TW - 1) / TC_TW, tiles_h = (Hi + TC_TH - 1) / TC_TH;
@@ -122,7 +123,7 @@ __global__ __launch_bounds__(256) void lvt_convt4_fwd_kernel(const float *__rest
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     const float v = (c < Cr) ? acc[q][rh][rw][c] + bias[c] : 0.f;
-                    o[rw][c] = act_tanh ? tanhf(v) : v;
+                    o[rw][c] = (act & LVT_EPI_TANH) ? tanhf(v) : (act & LVT_EPI_SIGMOID) ? lvt_sigmoid_col(v, c < Cr) : v;
                 }
                 o[rw][3] = 0.f;
             }
@@ -195,7 +196,7 @@ __device__ __forceinline__ float tm_scale(const float *amax, int &unscale) {    
 
 __global__ __launch_bounds__(TM_THREADS) void lvt_convt4_mfma_kernel(const float *__restrict__ x, const float *__restrict__ w,
                                                                      const float *__restrict__ bias, int N, int Hi, int Wi, int Cr,
-                                                                     int act_tanh, float *__restrict__ y,
+                                                                     int act, float *__restrict__ y,
                                                                      const float *__restrict__ x_amax, const float *__restrict__ w_amax) {
     __shared__ __attribute__((aligned(16))) unsigned short Wp[2 * TM_WPL];
     __shared__ __attribute__((aligned(16))) unsigned short Xp[2 * TM_XPL];
@@ -298,7 +299,8 @@ __global__ __launch_bounds__(TM_THREADS) void lvt_convt4_mfma_kernel(const float
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 float v = ldexpf(fmaf(acx[t][i], 1.f / 2048.f, acc[t][i]), unscale) + bias_c;
-                if (act_tanh) v = tanhf(v);
+                if (act & LVT_EPI_TANH) v = tanhf(v);
+                if (act & LVT_EPI_SIGMOID) v = lvt_sigmoidf(v);
                 if (c_ >= Cr) v = 0.f;
                 const int qh = ch0 + wave, qw = cw0 + 16 * t + 4 * kq + i;
                 y[(((long long)cimg * Ho + 2 * qh + rh) * Wo + 2 * qw + rw) * 4 + c_] = v;
@@ -443,8 +445,9 @@ int lvt_conv4s2_img_launch(const lvt_conv_geom *g, const float *x, const float *
     return LVT_OK;
 }
 
-extern "C" int lvt_convt4_fwd(const float *x, const float *w, const float *bias, int N, int Hi, int Wi, int Ci, int Cr,
-                              int act_tanh, float *y, int flags, const lvt_amax_io *ax, void *stream) {
+extern "C" int lvt_convt4_fwd_act(const float *x, const float *w, const float *bias, int N, int Hi, int Wi, int Ci, int Cr,
+                                  int act, float *y, int flags, const lvt_amax_io *ax, void *stream) {
+    LVT_REQUIRE(act == 0 || act == LVT_EPI_TANH || act == LVT_EPI_SIGMOID, "convT4_fwd: act must be 0, LVT_EPI_TANH or LVT_EPI_SIGMOID");
     LVT_REQUIRE(x && w && bias && y && N > 0 && Hi > 0 && Wi > 0, "convT4_fwd: bad args");
     LVT_REQUIRE(Ci % TC_CK == 0 && Cr >= 1 && Cr <= 3, "convT4_fwd: needs Ci %% 16 == 0 and 1..3 output channels");
     LVT_REQUIRE(!(flags & LVT_MATH_F16X2) || (ax && ax->a && ax->b), "convT4_fwd: LVT_MATH_F16X2 needs ax->a = max |x|, ax->b = max |w|");
@@ -453,14 +456,19 @@ extern "C" int lvt_convt4_fwd(const float *x, const float *w, const float *bias,
         const long long nbands = (long long)N * (Hi / TM_R) * (Wi / TM_W);
         const unsigned grid = (unsigned)(nbands < LVT_NUM_CU ? nbands : LVT_NUM_CU);       // persistent: one workgroup per CU
         hipLaunchKernelGGL(lvt_convt4_mfma_kernel, dim3(grid), dim3(TM_THREADS), 0, (hipStream_t)stream, x, w, bias, N, Hi, Wi, Cr,
-                           act_tanh, y, ax->a, ax->b);
+                           act, y, ax->a, ax->b);
         LVT_CHECK_LAUNCH("lvt_convt4_mfma_kernel");
         return LVT_OK;
     }
     const long long blocks = (long long)N * lvt_cdiv(Hi, TC_TH) * lvt_cdiv(Wi, TC_TW);
     LVT_REQUIRE(blocks < 0x7fffffffLL, "convT4_fwd: grid too large");
     hipLaunchKernelGGL(lvt_convt4_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, w, bias, N,
-                       Hi, Wi, Ci, Cr, act_tanh, y);
+                       Hi, Wi, Ci, Cr, act, y);
     LVT_CHECK_LAUNCH("lvt_convt4_fwd_kernel");
     return LVT_OK;
+}
+
+extern "C" int lvt_convt4_fwd(const float *x, const float *w, const float *bias, int N, int Hi, int Wi, int Ci, int Cr,
+                              int act_tanh, float *y, int flags, const lvt_amax_io *ax, void *stream) {
+    return lvt_convt4_fwd_act(x, w, bias, N, Hi, Wi, Ci, Cr, act_tanh ? LVT_EPI_TANH : 0, y, flags, ax, stream);
 }

@@ -13,8 +13,16 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get("LVT_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "liblvt_hip.so")
 
 EPI_BIAS, EPI_RESIDUAL, EPI_RELU, EPI_TANH, EPI_MASK, EPI_ACCUM, EPI_PLANES = 1, 2, 4, 8, 16, 32, 64
+EPI_SIGMOID = 128
+
+
+def epi_pad(n):
+    """LVT_EPI_PAD(n): the last n (0..3) output channels are zero pads, which a sigmoid epilogue stores as 0."""
+    if not 0 <= n <= 3:
+        raise ValueError("epi_pad: 0..3 pad channels, got %r" % (n,))
+    return n << 24
 CAUSAL_KMAX, CAUSAL_KMIN, CAUSAL_TILE = 1 << 8, 1 << 9, 1 << 10      # causal attention products (include/lvt_hip.h)
-ABI_VERSION = 640           # lvt_version() of the library this module binds (argument lists below)
+ABI_VERSION = 650           # lvt_version() of the library this module binds (argument lists below)
 MATH_F32 = 1 << 16          # per-call arithmetic selectors of the engine entry points (include/lvt_hip.h)
 MATH_F16X2 = 1 << 18
 ONEHOT_DENSE = 1 << 19
@@ -149,6 +157,7 @@ def _declare(lib):
         "lvt_conv3d_bwd_weight_fuses_bias": (ci, [P(ConvGeom), ci]),
         "lvt_conv3d_bwd_weight": (ci, [P(ConvGeom), vp, vp, vp, vp, ci, ci, ci, P(AmaxIO), vp, sz, vp]),
         "lvt_convt4_fwd": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, ci, vp, vp]),
+        "lvt_convt4_fwd_act": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, ci, vp, vp]),
         "lvt_colsum_workspace_bytes": (sz, [cll, ci]),
         "lvt_colsum": (ci, [vp, cll, ci, cll, vp, vp, sz, vp]),
         "lvt_vq_nearest_workspace_bytes": (sz, [cll, ci, ci]),
@@ -166,6 +175,7 @@ def _declare(lib):
         "lvt_l1_fwd": (ci, [vp, vp, cll, C.c_double, cf, vp, vp, sz, vp]),
         "lvt_l1_bwd": (ci, [vp, vp, cll, C.c_double, cf, vp, vp, ci, vp, vp, vp]),
         "lvt_tanh_bwd": (ci, [vp, vp, cll, vp, vp, vp]),
+        "lvt_sigmoid_bwd": (ci, [vp, vp, cll, vp, vp, vp]),
         "lvt_axpy": (ci, [vp, vp, cll, vp, cf, vp, vp]),
         "lvt_add_periodic": (ci, [vp, vp, cll, ci, ci, vp]),
         "lvt_layernorm_fwd": (ci, [vp, cll, ci, cf, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

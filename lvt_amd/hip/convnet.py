@@ -1,4 +1,4 @@
-"""Fused conv-stack executor: runs a chain of (transposed) convolutions with bias / ReLU / tanh /
+"""Fused conv-stack executor: runs a chain of (transposed) convolutions with bias / ReLU / tanh / sigmoid /
 residual epilogues on the implicit-GEMM engine, and its hand-scheduled backward.
 
 Every activation is stored once, post-activation and channels-last.  ReLU backward is folded into
@@ -32,8 +32,8 @@ class Layer:
 
     kind: "conv" | "convT".  For convT the geometry is that of the equivalent forward conv whose
     backward-data IS this layer (Ci = out channels of the ConvTranspose, Co = its in channels).
-    act: "" | "relu" | "tanh".  res_from: index of an earlier output added before the activation
-    (-1: none).  ci_real / co_real: channel counts of the torch-layout weight (pads excluded).
+    act: "" | "relu" | "tanh" | "sigmoid" (the last two on the last layer of a stack only).  res_from: index of an earlier
+    output added before the activation (-1: none).  ci_real / co_real: channel counts of the torch-layout weight (pads excluded).
     norm: "" | "bn" | "syncbn" | "frozen": batch normalisation between the conv and the residual add / activation; the
     module that holds its tensors is handed to stack_forward per call (`norms`).
     """
@@ -68,8 +68,12 @@ def _padded_bias(layer, b):
     return torch.cat([b, b.new_zeros(co - b.numel())])
 
 
-def _act_flag(act):
-    return {"": 0, "relu": L.EPI_RELU, "tanh": L.EPI_TANH}[act]
+def _act_flag(ly):
+    """Epilogue flags of the layer's activation.  sigmoid(0) is not 0: its flag carries the number of pad channels, which the
+    kernels then store as 0 like every other epilogue does by itself."""
+    if ly.act == "sigmoid":
+        return L.EPI_SIGMOID | L.epi_pad(Layer.pad4(ly.cout) - ly.cout)
+    return {"": 0, "relu": L.EPI_RELU, "tanh": L.EPI_TANH}[ly.act]
 
 
 def _world():
@@ -112,7 +116,7 @@ def _normalise(ly, nm, y, res):
     else:
         scale, shift, saved = _running_affine(ly, nm)
         nranks, batch = 1, False
-    out = BN.apply(y, scale, shift, res=res, act=_act_flag(ly.act))
+    out = BN.apply(y, scale, shift, res=res, act=_act_flag(ly))
     return out, (scale, saved, batch, nranks)
 
 
@@ -182,12 +186,12 @@ def stack_forward(layers, x, params, want_grad=True, norms=None):
             continue
         bias = _padded_bias(ly, b)
         if ly.kind == "conv":
-            y = G.conv_fwd(g, cur, wp, bias=bias, res=res, flags=_act_flag(ly.act), wq=wq)
+            y = G.conv_fwd(g, cur, wp, bias=bias, res=res, flags=_act_flag(ly), wq=wq)
         elif (ly.cout <= 3 and ly.kernel == (1, 4, 4) and ly.stride == (1, 2, 2) and ly.pad == (0, 1, 1)
-              and ly.cin % 16 == 0 and res is None and ly.act in ("", "tanh")):
-            y = G.convT4_fwd(cur, w, b, ly.act == "tanh")          # image-side layer: dedicated kernel
+              and ly.cin % 16 == 0 and res is None and ly.act in ("", "tanh", "sigmoid")):
+            y = G.convT4_fwd(cur, w, b, _act_flag(ly) & (L.EPI_TANH | L.EPI_SIGMOID))          # image-side layer: dedicated kernel
         else:
-            y = G.conv_bwd_data(g, cur, wp, bias=bias, res=res, flags=_act_flag(ly.act), wph=wph)
+            y = G.conv_bwd_data(g, cur, wp, bias=bias, res=res, flags=_act_flag(ly), wph=wph)
         outs.append(y)
         cur = y
     return outs, (geoms, packed, norms, pre, bn_saved)
@@ -220,6 +224,8 @@ def stack_backward(layers, x, outs, saved, grad_out, need_input_grad=False):
     last = layers[-1]
     if last.act == "tanh":
         gpre = ew.tanh_bwd(grad_out, outs[-1])
+    elif last.act == "sigmoid":
+        gpre = ew.sigmoid_bwd(grad_out, outs[-1])
     elif last.act == "relu":
         raise L.LvtError("a ReLU-terminated stack is not used by the reference architectures")
     else:
@@ -261,8 +267,8 @@ def stack_backward(layers, x, outs, saved, grad_out, need_input_grad=False):
         prev = layers[i - 1] if i > 0 else None
         res = gpres[res_user[i - 1]] if (i - 1) in res_user else None
         mask = outs[i - 1] if (prev is not None and prev.act == "relu") else None
-        if prev is not None and prev.act == "tanh":
-            raise L.LvtError("tanh is only supported on the last layer of a stack")
+        if prev is not None and prev.act in ("tanh", "sigmoid"):
+            raise L.LvtError("%s is only supported on the last layer of a stack" % prev.act)
         if ly.kind == "conv":
             gin = G.conv_bwd_data(g, gp, wp, res=res, mask=mask, wt=wt, wph=wph)
         else:

@@ -59,6 +59,14 @@ def tanh_bwd(g, y):
     return out
 
 
+def sigmoid_bwd(g, y):
+    """g * y * (1 - y) from the saved sigmoid output y.  Reports max |out| (f16x2 mode)."""
+    L.require(g, y)
+    out = torch.empty_like(g)
+    L.check(L.lib().lvt_sigmoid_bwd(L.ptr(g), L.ptr(y), g.numel(), L.ptr(out), L.out_amax(out), L.stream_ptr()), "lvt_sigmoid_bwd")
+    return out
+
+
 def axpy(x, alpha=1.0, alpha_dev=None, add=None):
     L.require(x, alpha_dev, add)
     out = torch.empty_like(x)

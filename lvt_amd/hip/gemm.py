@@ -436,16 +436,17 @@ def conv_bwd_data(g, dy, wp, bias=None, res=None, mask=None, flags=0, wt=None, w
     return dx
 
 
-def convT4_fwd(x, w, bias, act_tanh):
+def convT4_fwd(x, w, bias, act=0):
     """ConvTranspose2d(Ci -> <=3, k4 s2 p1) forward on the dedicated image-side kernel.
-    x (N,1,Hi,Wi,Ci) -> (N,1,2Hi,2Wi,4)."""
+    x (N,1,Hi,Wi,Ci) -> (N,1,2Hi,2Wi,4).  act: 0, binding.EPI_TANH or binding.EPI_SIGMOID (True / False: tanh / none)."""
+    act = L.EPI_TANH if act is True else int(act)
     L.require(x, w, bias)
     N, _, Hi, Wi, Ci = x.shape
     y = torch.empty(N, 1, 2 * Hi, 2 * Wi, 4, dtype=torch.float32, device=x.device)
     io = L.amax_io(x, w)
     t0 = L.TIMER.begin() if L.TIMER is not None else None
-    L.check(L.lib().lvt_convt4_fwd(L.ptr(x), L.ptr(w), L.ptr(bias), N, Hi, Wi, Ci, w.shape[1], 1 if act_tanh else 0,
-                                   L.ptr(y), L.math_flag(), L.io_ref(io), L.stream_ptr()), "lvt_convt4_fwd")
+    L.check(L.lib().lvt_convt4_fwd_act(L.ptr(x), L.ptr(w), L.ptr(bias), N, Hi, Wi, Ci, w.shape[1], act,
+                                       L.ptr(y), L.math_flag(), L.io_ref(io), L.stream_ptr()), "lvt_convt4_fwd_act")
     if t0 is not None:
         L.TIMER.end("thin_convT_fwd", 2.0 * N * 4 * Hi * Wi * 4 * 4 * Ci, t0)
     return y

@@ -87,6 +87,28 @@ class _LayoutOut(torch.autograd.Function):
 
 
 SUPPORTED_NORMS = ("", "BN", "SyncBN", "FrozenBN")
+_OUT_ACTIVATIONS = {"": None, "sigmoid": nn.Sigmoid, "tanh": nn.Tanh}
+
+
+def out_activation_module(name):
+    """The module the reference appends as the last child of `layers` for OUT_ACTIVATION `name` (None for ""; it has no
+    state-dict keys), or ValueError for a string the reference does not know either."""
+    if name not in _OUT_ACTIVATIONS:
+        raise ValueError("Unknown activation %r" % (name,))
+    cls = _OUT_ACTIVATIONS[name]
+    return cls() if cls is not None else None
+
+
+def act_after(nxt):
+    """Activation the plan folds into the layer whose output the module `nxt` consumes: an explicit ReLU or a ResBlock
+    (whose first op is an in-place ReLU) rectifies it, a trailing Tanh / Sigmoid is the stack's output activation."""
+    if isinstance(nxt, (nn.ReLU, ResBlock)):
+        return "relu"
+    if isinstance(nxt, nn.Tanh):
+        return "tanh"
+    if isinstance(nxt, nn.Sigmoid):
+        return "sigmoid"
+    return ""
 
 
 def check_norm(norm, spectral):

@@ -3,7 +3,7 @@
 Same constructor / `from_config` / state_dict keys (`layers.N.weight`, `layers.N.block.M.weight`);
 the forward pass is one fused chain of implicit-GEMM kernels on channels-last activations:
 
-    stride 4:  Conv(k4 s2 p1)+ReLU, Conv(k4 s2 p1)+ReLU, Conv(k3 p1), n x ResBlock
+    stride 4:  Conv(k4 s2 p1)+ReLU, Conv(k4 s2 p1)+ReLU, Conv(k3 p1), n x ResBlock [, sigmoid | tanh]
 
 The reference's ResBlock starts with an in-place ReLU, so the block input itself is rectified and
 the skip adds relu(x).  That ReLU is therefore folded into the epilogue of the layer
@@ -29,8 +29,10 @@ class ResEncoder(Encoder):
     def __init__(self, in_channels, nf, res_channels, norm, use_spectral_norm, n_layers, out_activation, stride):
         super().__init__()
         convstack.check_norm(norm, use_spectral_norm)
-        if out_activation != "":
-            raise NotImplementedError("ResEncoder out_activation %r is not used by any shipped config" % out_activation)
+        if out_activation == "relu":
+            # the reference's encoder also knows "relu"; a ReLU-terminated stack has no backward here (hip/convnet.py)
+            raise NotImplementedError("ResEncoder out_activation 'relu' is not implemented")
+        out_act = convstack.out_activation_module(out_activation)
         norm = norm or ""
         nl = convstack.norm_layer
         if stride == 4:
@@ -41,6 +43,8 @@ class ResEncoder(Encoder):
         else:
             raise ValueError
         mods += [convstack.ResBlock(nf, res_channels, norm) for _ in range(n_layers)]
+        if out_act is not None:
+            mods.append(out_act)
         self.layers = nn.Sequential(*mods)
         self.in_channels, self.out_channels = in_channels, nf
         self._plan = self._build_plan()
@@ -51,13 +55,14 @@ class ResEncoder(Encoder):
         plan, owners, norms = [], [], []
         for i, m in enumerate(mods):
             nxt = mods[i + 1] if i + 1 < len(mods) else None
-            # this output is rectified if an explicit ReLU or a ResBlock (in-place ReLU) follows
-            relu_after = isinstance(nxt, (nn.ReLU, convstack.ResBlock))
+            # this output is rectified if an explicit ReLU or a ResBlock (in-place ReLU) follows, bounded if the output
+            # activation does
+            act = convstack.act_after(nxt)
             if convstack.is_conv(m, nn.Conv2d):
                 m, nm, kind = convstack.split_norm(m)
                 k, s, p = m.kernel_size[0], m.stride[0], m.padding[0]
                 plan.append(Layer("conv", (1, k, k), (1, s, s), (0, p, p), m.in_channels, m.out_channels,
-                                  act="relu" if relu_after else "", norm=kind))
+                                  act=act, norm=kind))
                 owners.append(m)
                 norms.append(nm)
             elif isinstance(m, convstack.ResBlock):
@@ -69,7 +74,7 @@ class ResEncoder(Encoder):
                 norms.append(n3)
                 # the residual is added after the second norm: relu(x) + BN(conv1x1(relu(BN(conv3x3(relu(x))))))
                 plan.append(Layer("conv", (1, 1, 1), (1, 1, 1), (0, 0, 0), c1.in_channels, c1.out_channels,
-                                  act="relu" if relu_after else "", res_from=src, norm=k1))
+                                  act=act, res_from=src, norm=k1))
                 owners.append(c1)
                 norms.append(n1)
         self._owners = owners

@@ -1,6 +1,6 @@
 """Residual conv decoder (reference: vidgen/modeling/generator/resdecoder.py:25-75).
 
-    Conv(k3 p1), n x ResBlock, ReLU, ConvT(k4 s2 p1)+ReLU, ConvT(k4 s2 p1), tanh
+    Conv(k3 p1), n x ResBlock, ReLU, ConvT(k4 s2 p1)+ReLU, ConvT(k4 s2 p1) [, tanh | sigmoid]
 
 ConvTranspose layers run as the backward-data form of the implicit-GEMM engine, decomposed by
 output stride phase so that no matrix-core work is spent on structurally-zero taps.
@@ -40,10 +40,9 @@ class ResDecoder(Generator):
             mods += [nl(nn.ConvTranspose2d(nf, out_channels, 4, 2, 1), norm)]
         else:
             raise ValueError
-        if out_activation == "tanh":
-            mods.append(nn.Tanh())
-        elif out_activation != "":
-            raise NotImplementedError("ResDecoder out_activation %r is not used by any shipped config" % out_activation)
+        out_act = convstack.out_activation_module(out_activation)
+        if out_act is not None:
+            mods.append(out_act)
         self.layers = nn.Sequential(*mods)
         self.in_channels, self.out_channels = in_channels, out_channels
         self._plan = self._build_plan()
@@ -53,12 +52,7 @@ class ResDecoder(Generator):
         plan, owners, norms = [], [], []
         for i, m in enumerate(mods):
             nxt = mods[i + 1] if i + 1 < len(mods) else None
-            if isinstance(nxt, (nn.ReLU, convstack.ResBlock)):
-                act = "relu"
-            elif isinstance(nxt, nn.Tanh):
-                act = "tanh"
-            else:
-                act = ""
+            act = convstack.act_after(nxt)
             if convstack.is_conv(m, nn.Conv2d) or convstack.is_conv(m, nn.ConvTranspose2d):
                 m, nm, kind = convstack.split_norm(m)
                 k, s, p = m.kernel_size[0], m.stride[0], m.padding[0]
