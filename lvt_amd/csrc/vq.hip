@@ -772,74 +772,103 @@ __global__ void lvt_vq_nearest_merge_kernel(const float *__restrict__ pbest, con
     idx_out[((row / P) * num + g) * (long long)P + row % P] = bi;
 }
 
-// out[row][g*D + d] = E[g][idx[n][g][p]][d]  (D == 64).  16 lanes move one (row, g) slice as float4, so a wave
-// writes 1 KB of consecutive output per step (a whole row when num == 4) and every lane keeps GATHER_UNROLL
-// independent index -> codebook -> store chains in flight; one lane per float with a single chain per wave ran at
-// 1.75 TB/s of the 134 MB it writes.
+// out[row][g*D + d] = E[g][idx[n][g][p]][d] for any D % 4 == 0 (DT = 64: the width at compile time, DT = 0: from `d_arg`).
+// D / 4 lanes move one (row, g) slice as float4 -- at D = 64 a wave writes 1 KB of consecutive output per step (a whole row
+// when num == 4) -- and every lane keeps GATHER_UNROLL independent index -> codebook -> store chains in flight; one lane per
+// float with a single chain per wave ran at 1.75 TB/s of the 134 MB it writes.
 #define GATHER_UNROLL 4
+template <int DT>
 __global__ __launch_bounds__(256) void lvt_vq_gather_kernel(const long long *__restrict__ idx,
                                                             const float *__restrict__ codebooks, long long rows, int num,
-                                                            int KC, int P, float *__restrict__ out, int ldo) {
-    const long long pairs = rows * num;
-    const int q = threadIdx.x & 15;                                   // float4 within the 64-float slice
-    const long long stride = ((long long)gridDim.x * blockDim.x) >> 4;
-    for (long long pr = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 4; pr < pairs; pr += stride * GATHER_UNROLL) {
-        long long k[GATHER_UNROLL], row[GATHER_UNROLL]; int g[GATHER_UNROLL];
+                                                            int d_arg, int KC, int P, float *__restrict__ out, int ldo) {
+    const int D = DT ? DT : d_arg;
+    const int Q = D / 4;
+    const long long items = rows * num * Q;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long it = (long long)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride * GATHER_UNROLL) {
+        long long k[GATHER_UNROLL], row[GATHER_UNROLL]; int g[GATHER_UNROLL], q[GATHER_UNROLL];
 #pragma unroll
         for (int u = 0; u < GATHER_UNROLL; ++u) {
-            const long long pu = pr + stride * u;
-            row[u] = pu / num; g[u] = (int)(pu % num);
-            k[u] = pu < pairs ? idx[((row[u] / P) * num + g[u]) * (long long)P + row[u] % P] : 0;
+            const long long iu = it + stride * u, pr = iu / Q;
+            q[u] = (int)(iu - pr * Q); row[u] = pr / num; g[u] = (int)(pr - row[u] * num);
+            k[u] = iu < items ? idx[((row[u] / P) * num + g[u]) * (long long)P + row[u] % P] : 0;
         }
         float4 v[GATHER_UNROLL];
 #pragma unroll
         for (int u = 0; u < GATHER_UNROLL; ++u)
-            v[u] = *reinterpret_cast<const float4 *>(codebooks + ((long long)g[u] * KC + k[u]) * VQ_D + q * 4);
+            v[u] = *reinterpret_cast<const float4 *>(codebooks + ((long long)g[u] * KC + k[u]) * D + q[u] * 4);
 #pragma unroll
         for (int u = 0; u < GATHER_UNROLL; ++u)
-            if (pr + stride * u < pairs) *reinterpret_cast<float4 *>(out + row[u] * ldo + g[u] * VQ_D + q * 4) = v[u];
+            if (it + stride * u < items) *reinterpret_cast<float4 *>(out + row[u] * ldo + (long long)g[u] * D + q[u] * 4) = v[u];
     }
 }
 
 // EMA statistics: stats[g][k][0..D-1] = sum of the rows assigned to code k, stats[g][k][D] = their count.
-// A workgroup owns one (group, row chunk) and keeps a PRIVATE 512 x 65 accumulator in LDS (133 KB of the
-// 160 KB).  Wave w only accumulates rows whose code is congruent to w mod 8, walking them in row order:
-// no two waves ever touch the same accumulator row, no atomics are needed, and the summation order is a
-// pure function of the data (bit-reproducible).  Chunk partials are then summed in chunk order.
+// A workgroup owns one (group, code range [k0, k0 + Kt), row chunk) and keeps a PRIVATE Kt x (D + 1) accumulator in LDS beside
+// a 64-row staging tile.  Two instantiation families:
+//   <64, KCT>, KCT = 512 | 256 | 128: the whole codebook is the one range (512 x 65 floats = 133 KB of the 160 KB); no range
+//             test, and the z rows are fetched without looking at their index.
+//   <0, 0>:   run-time D, KC, Kt with Kt = 64 * floor(72 KB / (4 (D + 1)) / 64) (1024 codes at D = 16, 256 at D = 64, 64 at
+//             D = 256).  The workgroup reads the chunk's indices and only the z rows whose code lies in its range: z is still
+//             read once in all, the index traffic repeats per code range.
+// Rows of a tile that share a code are summed in row order by ONE wave (below): no two waves ever touch the same accumulator
+// row, no atomics are needed, and the summation order is a pure function of the data (bit-reproducible).  Chunk partials
+// [g][chunk][KC][D + 1] are then summed in chunk order by lvt_vq_ema_reduce_kernel.
 #define EMA_THREADS 512
-template <int KC>
+#define EMA_ROWS 64
+#define EMAG_ACC_BYTES 73728
+#define EMAG_MAXCH 8                        // staged float4 per thread at a run-time D: 64 rows x D / 4 <= 4096 at D = 256
+template <int DT, int KCT>
 __global__ __launch_bounds__(EMA_THREADS) void lvt_vq_ema_partial_kernel(
-    const long long *__restrict__ idx, const float *__restrict__ z, long long rows, int ldz, int num, int P,
-    long long rows_per_chunk, int nchunks, float *__restrict__ partial) {
-    constexpr int LDS_LD = VQ_D + 1;
-    extern __shared__ __attribute__((aligned(16))) float acc[];      // [KC][65], then a 64-row staging tile
-    float *tile = acc + ((KC * LDS_LD + 3) & ~3);                   // [64 rows][VQ_D]
-    const int g = blockIdx.x / nchunks, c = blockIdx.x % nchunks;
+    const long long *__restrict__ idx, const float *__restrict__ z, long long rows, int ldz, int num, int d_arg, int kc_arg,
+    int P, int kt_arg, long long rows_per_chunk, int nchunks, float *__restrict__ partial) {
+    constexpr bool WHOLE = KCT > 0;
+    static_assert(!WHOLE || DT > 0, "a whole-codebook accumulator needs a compile-time width");
+    constexpr int NCH = DT ? EMA_ROWS * (DT / 4) / EMA_THREADS : EMAG_MAXCH;     // staged float4 per thread
+    static_assert(DT == 0 || NCH * EMA_THREADS == EMA_ROWS * (DT / 4), "staging tile");
+    const int D = DT ? DT : d_arg, KC = WHOLE ? KCT : kc_arg, Kt = WHOLE ? KCT : kt_arg;
+    const int LD = D + 1, Q = D / 4;
+    extern __shared__ __attribute__((aligned(16))) float acc[];      // [Kt][D + 1], then the staging tile [64][D]
+    float *tile = acc + ((Kt * LD + 3) & ~3);
+    const int g = blockIdx.y, c = blockIdx.x % nchunks, k0 = WHOLE ? 0 : (blockIdx.x / nchunks) * Kt;
+    const int kn = KC - k0 < Kt ? KC - k0 : Kt;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = tid; i < KC * LDS_LD; i += EMA_THREADS) acc[i] = 0.f;
+    for (int i = tid; i < kn * LD; i += EMA_THREADS) acc[i] = 0.f;
     const long long r0 = (long long)c * rows_per_chunk;
     const long long r1 = min(rows, r0 + rows_per_chunk);
-    // 64 rows at a time: the workgroup fetches them coalesced (16 lanes per 256-byte row slice, the next tile is in
-    // flight in registers), then the waves reduce them from LDS -- no wave waits on a global load per row any more.
-    const int trow = tid >> 4, tq = (tid & 15) * 4;                  // staging: rows trow and trow + 32
-    float4 pre[2];
+    auto code_of = [&](long long r) -> int {                        // code - k0 inside the range, else -1
+        if (r >= r1) return -1;
+        const long long k = idx[((r / P) * num + g) * (long long)P + r % P];
+        if constexpr (WHOLE) return (int)k;
+        return k >= k0 && k < k0 + kn ? (int)(k - k0) : -1;
+    };
+    // 64 rows at a time: the workgroup fetches them coalesced (D / 4 lanes per row slice, the next tile is in flight in
+    // registers), then the waves reduce them from LDS -- no wave waits on a global load per row.  Of a ranged scan only the
+    // rows of this range are fetched (the others stay zero in the tile and are never read).
+    float4 pre[NCH];
     auto fetch = [&](long long base) {
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const long long r = base + trow + 32 * u;
-            pre[u] = r < r1 ? *reinterpret_cast<const float4 *>(z + r * (long long)ldz + g * VQ_D + tq) : make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int u = 0; u < NCH; ++u) {
+            const int e = tid + u * EMA_THREADS;
+            pre[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (e < EMA_ROWS * Q) {
+                const int rr = e / Q, q = e % Q;
+                if (WHOLE ? base + rr < r1 : code_of(base + rr) >= 0)
+                    pre[u] = *reinterpret_cast<const float4 *>(z + (base + rr) * (long long)ldz + (long long)g * D + 4 * q);
+            }
         }
     };
     if (r0 < r1) fetch(r0);
     __syncthreads();
-    for (long long base = r0; base < r1; base += 64) {
+    for (long long base = r0; base < r1; base += EMA_ROWS) {
 #pragma unroll
-        for (int u = 0; u < 2; ++u) *reinterpret_cast<float4 *>(&tile[(trow + 32 * u) * VQ_D + tq]) = pre[u];
-        const long long r = base + lane;
-        int code = -1;
-        if (r < r1) code = (int)idx[((r / P) * num + g) * (long long)P + r % P];
+        for (int u = 0; u < NCH; ++u) {
+            const int e = tid + u * EMA_THREADS;
+            if (e < EMA_ROWS * Q) *reinterpret_cast<float4 *>(&tile[(e / Q) * D + 4 * (e % Q)]) = pre[u];
+        }
+        const int code = code_of(base + lane);
         __syncthreads();
-        if (base + 64 < r1) fetch(base + 64);
+        if (base + EMA_ROWS < r1) fetch(base + EMA_ROWS);
         // Rows of the tile that share a code are summed in registers first and hit the LDS accumulator once, by
         // the wave that owns the code's FIRST row in the tile (row j belongs to wave j & 7): no two waves ever touch
         // the same accumulator row inside a tile, the work is spread by rows (a skewed code histogram no longer
@@ -851,17 +880,19 @@ __global__ __launch_bounds__(EMA_THREADS) void lvt_vq_ema_partial_kernel(
             const unsigned long long same = __ballot(code == cj);
             todo &= ~same;
             if ((j & 7) != wave) continue;
-            float sum = 0.f; int cnt = 0;
-            unsigned long long mm = same;
-            while (mm) { const int r_ = __ffsll((long long)mm) - 1; mm &= mm - 1; sum += tile[r_ * VQ_D + lane]; ++cnt; }
-            acc[cj * LDS_LD + lane] += sum;
-            if (lane == 0) acc[cj * LDS_LD + VQ_D] += (float)cnt;
+            for (int d = lane; d < D; d += 64) {
+                float sum = 0.f;
+                unsigned long long mm = same;
+                while (mm) { const int r_ = __ffsll((long long)mm) - 1; mm &= mm - 1; sum += tile[r_ * D + d]; }
+                acc[cj * LD + d] += sum;
+            }
+            if (lane == 0) acc[cj * LD + D] += (float)__popcll(same);
         }
         __syncthreads();
     }
     __syncthreads();
-    float *dst = partial + ((long long)g * nchunks + c) * (KC * LDS_LD);
-    for (int i = tid; i < KC * LDS_LD; i += EMA_THREADS) dst[i] = acc[i];
+    float *dst = partial + ((long long)g * nchunks + c) * ((long long)KC * LD) + (long long)k0 * LD;
+    for (int i = tid; i < kn * LD; i += EMA_THREADS) dst[i] = acc[i];
 }
 
 // stats[g][i] = sum_c partial[g][c][i]  (chunk order)
@@ -885,22 +916,24 @@ __global__ void lvt_vq_ema_reduce_kernel(const float *__restrict__ partial, int 
     stats[(long long)g * per_group + i] = s;
 }
 
-// one workgroup per codebook group (vq_embedding.py:48-59)
-__global__ __launch_bounds__(512) void lvt_vq_ema_finalize_kernel(const float *__restrict__ stats, int KC,
+// one workgroup per codebook group (vq_embedding.py:48-59); DT = 64: the width at compile time, DT = 0: from `d_arg`
+template <int DT>
+__global__ __launch_bounds__(512) void lvt_vq_ema_finalize_kernel(const float *__restrict__ stats, int KC, int d_arg,
                                                                   float decay, float one_minus_decay, float eps,
                                                                   float *__restrict__ running_size,
                                                                   float *__restrict__ running_sum,
                                                                   float *__restrict__ weight) {
+    const int D = DT ? DT : d_arg;
     __shared__ float red[512];
     __shared__ float ntot;
     const int g = blockIdx.x, tid = threadIdx.x;
     float *rs = running_size + (long long)g * KC;
-    float *rsum = running_sum + (long long)g * KC * VQ_D;
-    float *w = weight + (long long)g * KC * VQ_D;
-    const float *st = stats + (long long)g * KC * (VQ_D + 1);
+    float *rsum = running_sum + (long long)g * KC * D;
+    float *w = weight + (long long)g * KC * D;
+    const float *st = stats + (long long)g * KC * (D + 1);
     float part = 0.f;
     for (int k = tid; k < KC; k += blockDim.x) {
-        const float v = rs[k] * decay + one_minus_decay * st[k * (VQ_D + 1) + VQ_D];
+        const float v = rs[k] * decay + one_minus_decay * st[k * (D + 1) + D];
         rs[k] = v;
         part += v;
     }
@@ -916,19 +949,20 @@ __global__ __launch_bounds__(512) void lvt_vq_ema_finalize_kernel(const float *_
     // 8 elements per thread and pass, all loads issued before the first use: with one element per pass every
     // iteration paid a full memory latency (64 dependent round trips per thread, 38 us for 128 K floats)
     constexpr int FB = 8;
-    for (int i0 = tid; i0 < KC * VQ_D; i0 += blockDim.x * FB) {
+    const int tot = KC * D;
+    for (int i0 = tid; i0 < tot; i0 += blockDim.x * FB) {
         float a[FB], b[FB], c[FB];
 #pragma unroll
         for (int u = 0; u < FB; ++u) {
             const int i = i0 + u * blockDim.x;
-            const bool ok = i < KC * VQ_D;
-            const int k = ok ? i / VQ_D : 0, d = i % VQ_D;
-            a[u] = ok ? rsum[i] : 0.f; b[u] = st[k * (VQ_D + 1) + d]; c[u] = rs[k];
+            const bool ok = i < tot;
+            const int k = ok ? i / D : 0, d = DT || ok ? i % D : 0;     // (past the end: unused; a run-time D skips the division)
+            a[u] = ok ? rsum[i] : 0.f; b[u] = st[k * (D + 1) + d]; c[u] = rs[k];
         }
 #pragma unroll
         for (int u = 0; u < FB; ++u) {
             const int i = i0 + u * blockDim.x;
-            if (i < KC * VQ_D) {
+            if (i < tot) {
                 const float s = a[u] * decay + one_minus_decay * b[u];
                 rsum[i] = s;
                 const float size_ = (c[u] + eps) / (n + KC * eps) * n;
@@ -971,12 +1005,11 @@ __global__ __launch_bounds__(512) void lvt_vq_ema_finalize_kernel(const float *_
 //     (D / 2) half .. + D / 2 - 1 of its row (128 VGPRs at D = 256) and a running (max, argmax) of 16 rows for its code column;
 //     five shuffle steps finish the row reduction.
 //
-// EMA statistics.  The LDS-private accumulator of lvt_vq_ema_partial_kernel cannot hold KC x (D + 1) floats any more, so a
-// workgroup owns (group, code range [k0, k0 + Kt), row chunk) with Kt = 64 * floor(72 KB / (4 (D + 1)) / 64) (1024 codes
-// at D = 16, 256 at D = 64, 64 at D = 256) beside a 64-row staging tile (64 D floats).  It reads the chunk's indices and
-// only the z rows whose code lies in its range: z is still read once in all, the index traffic repeats per code range.
-// Same fixed order as the specialised kernel (rows ascending inside a tile, tiles ascending, chunk partials summed in chunk
-// order by lvt_vq_ema_reduce_kernel): deterministic, atomic-free, bit-reproducible.
+// Gather, EMA statistics, EMA finalize.  One kernel each (above), instantiated for the compile-time width 64 and for a
+// run-time width; the statistics kernel for a whole codebook of 512 / 256 / 128 codes in LDS at D = 64 and, for everything
+// else, for code ranges of Kt codes.  Both families keep the same fixed order (rows ascending inside a tile, tiles
+// ascending, chunk partials summed in chunk order): deterministic, atomic-free, bit-reproducible.  vq_route() below says which
+// geometry takes which.
 // ================================================================================================
 #define VQG_TILE_BYTES 40960                 // one LDS code tile (two are resident: <= 80 KB, two workgroups per CU)
 // 8 waves per workgroup; 4 from D = 176 on, where a wave needs more than the 256 registers of 2 waves per SIMD
@@ -1273,156 +1306,48 @@ __global__ __launch_bounds__(vqg_threads<DG>()) void lvt_vq_nearest_gen_f32_kern
     }
 }
 
-// out[row][g*D + d] = E[g][idx][d] for any D % 4 == 0: D / 4 lanes move one (row, g) slice as float4, every lane keeps
-// GATHER_UNROLL independent index -> codebook -> store chains in flight (as lvt_vq_gather_kernel)
-__global__ __launch_bounds__(256) void lvt_vq_gather_gen_kernel(const long long *__restrict__ idx,
-                                                                const float *__restrict__ codebooks, long long rows, int num,
-                                                                int D, int KC, int P, float *__restrict__ out, int ldo) {
-    const int Q = D / 4;
-    const long long items = rows * num * Q;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long it = (long long)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride * GATHER_UNROLL) {
-        long long k[GATHER_UNROLL], row[GATHER_UNROLL]; int g[GATHER_UNROLL], q[GATHER_UNROLL];
-#pragma unroll
-        for (int u = 0; u < GATHER_UNROLL; ++u) {
-            const long long iu = it + stride * u, pr = iu / Q;
-            q[u] = (int)(iu - pr * Q); row[u] = pr / num; g[u] = (int)(pr - row[u] * num);
-            k[u] = iu < items ? idx[((row[u] / P) * num + g[u]) * (long long)P + row[u] % P] : 0;
-        }
-        float4 v[GATHER_UNROLL];
-#pragma unroll
-        for (int u = 0; u < GATHER_UNROLL; ++u)
-            v[u] = *reinterpret_cast<const float4 *>(codebooks + ((long long)g[u] * KC + k[u]) * D + q[u] * 4);
-#pragma unroll
-        for (int u = 0; u < GATHER_UNROLL; ++u)
-            if (it + stride * u < items) *reinterpret_cast<float4 *>(out + row[u] * ldo + (long long)g[u] * D + q[u] * 4) = v[u];
-    }
+// ---- host side ---------------------------------------------------------------------------------------------------------
+// Which kernel family serves a geometry (D = sub-vector width, KC = codes per group):
+//   d64   D == 64, any KC: gather and EMA finalize take their <64> instantiation (they only index with D); every other
+//         width takes <0>, which reads D from its argument.
+//   inst  D == 64 and KC in {512, 256, 128}: the search kernels that keep the whole codebook group in LDS and the
+//         whole-codebook statistics kernel <64, KC> exist for exactly these.  Everything else -- (64, 1024) too, which still
+//         gathers and finalizes on <64> -- searches on the generic kernels and accumulates on the ranged <0, 0>.
+struct VqRoute { bool d64, inst; };
+static VqRoute vq_route(int D, int KC) {
+    const bool d64 = D == VQ_D;
+    return {d64, d64 && (KC == 512 || KC == 256 || KC == 128)};
 }
-
-// EMA statistics of code range [k0, k0 + Kt) of group g over one row chunk (see the comment at the top of this section)
-#define EMAG_ROWS 64
-#define EMAG_ACC_BYTES 73728
-#define EMAG_MAXCH 8                        // staged float4 per thread: 64 rows x D / 4 <= 4096 at D = 256
-__global__ __launch_bounds__(EMA_THREADS) void lvt_vq_ema_partial_gen_kernel(
-    const long long *__restrict__ idx, const float *__restrict__ z, long long rows, int ldz, int num, int D, int KC, int P,
-    int Kt, long long rows_per_chunk, int nchunks, float *__restrict__ partial) {
-    extern __shared__ __attribute__((aligned(16))) float acc[];      // [Kt][D + 1], then the staging tile [64][D]
-    const int LD = D + 1, Q = D / 4;
-    float *tile = acc + ((Kt * LD + 3) & ~3);
-    const int g = blockIdx.y, c = blockIdx.x % nchunks, k0 = (blockIdx.x / nchunks) * Kt;
-    const int kn = KC - k0 < Kt ? KC - k0 : Kt;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = tid; i < kn * LD; i += EMA_THREADS) acc[i] = 0.f;
-    const long long r0 = (long long)c * rows_per_chunk;
-    const long long r1 = min(rows, r0 + rows_per_chunk);
-    auto code_of = [&](long long r) -> int {                        // code - k0 inside the range, else -1
-        if (r >= r1) return -1;
-        const long long k = idx[((r / P) * num + g) * (long long)P + r % P];
-        return k >= k0 && k < k0 + kn ? (int)(k - k0) : -1;
-    };
-    // only the rows of this range are fetched (the others stay zero in the tile and are never read)
-    float4 pre[EMAG_MAXCH];
-    auto fetch = [&](long long base) {
-#pragma unroll
-        for (int u = 0; u < EMAG_MAXCH; ++u) {
-            const int e = tid + u * EMA_THREADS;
-            pre[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (e < EMAG_ROWS * Q) {
-                const int rr = e / Q, q = e % Q;
-                if (code_of(base + rr) >= 0)
-                    pre[u] = *reinterpret_cast<const float4 *>(z + (base + rr) * (long long)ldz + (long long)g * D + 4 * q);
-            }
-        }
-    };
-    if (r0 < r1) fetch(r0);
-    __syncthreads();
-    for (long long base = r0; base < r1; base += EMAG_ROWS) {
-#pragma unroll
-        for (int u = 0; u < EMAG_MAXCH; ++u) {
-            const int e = tid + u * EMA_THREADS;
-            if (e < EMAG_ROWS * Q) *reinterpret_cast<float4 *>(&tile[(e / Q) * D + 4 * (e % Q)]) = pre[u];
-        }
-        const int code = code_of(base + lane);
-        __syncthreads();
-        if (base + EMAG_ROWS < r1) fetch(base + EMAG_ROWS);
-        // as lvt_vq_ema_partial_kernel: the rows of a code are summed in row order by the wave that owns the code's first row
-        unsigned long long todo = __ballot(code >= 0);
-        while (todo) {
-            const int j = __ffsll((long long)todo) - 1;
-            const int cj = __shfl(code, j);
-            const unsigned long long same = __ballot(code == cj);
-            todo &= ~same;
-            if ((j & 7) != wave) continue;
-            for (int d = lane; d < D; d += 64) {
-                float sum = 0.f;
-                unsigned long long mm = same;
-                while (mm) { const int r_ = __ffsll((long long)mm) - 1; mm &= mm - 1; sum += tile[r_ * D + d]; }
-                acc[cj * LD + d] += sum;
-            }
-            if (lane == 0) acc[cj * LD + D] += (float)__popcll(same);
-        }
-        __syncthreads();
-    }
-    __syncthreads();
-    float *dst = partial + ((long long)g * nchunks + c) * ((long long)KC * LD) + (long long)k0 * LD;
-    for (int i = tid; i < kn * LD; i += EMA_THREADS) dst[i] = acc[i];
-}
-
-// lvt_vq_ema_finalize_kernel for a runtime D
-__global__ __launch_bounds__(512) void lvt_vq_ema_finalize_gen_kernel(const float *__restrict__ stats, int KC, int D,
-                                                                      float decay, float one_minus_decay, float eps,
-                                                                      float *__restrict__ running_size,
-                                                                      float *__restrict__ running_sum,
-                                                                      float *__restrict__ weight) {
-    __shared__ float red[512];
-    __shared__ float ntot;
-    const int g = blockIdx.x, tid = threadIdx.x;
-    float *rs = running_size + (long long)g * KC;
-    float *rsum = running_sum + (long long)g * KC * D;
-    float *w = weight + (long long)g * KC * D;
-    const float *st = stats + (long long)g * KC * (D + 1);
-    float part = 0.f;
-    for (int k = tid; k < KC; k += blockDim.x) {
-        const float v = rs[k] * decay + one_minus_decay * st[k * (D + 1) + D];
-        rs[k] = v;
-        part += v;
-    }
-    red[tid] = part;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) ntot = red[0];
-    __syncthreads();
-    const float n = ntot;
-    constexpr int FB = 8;
-    const int tot = KC * D;
-    for (int i0 = tid; i0 < tot; i0 += blockDim.x * FB) {
-        float a[FB], b[FB], c[FB];
-#pragma unroll
-        for (int u = 0; u < FB; ++u) {
-            const int i = i0 + u * blockDim.x;
-            const bool ok = i < tot;
-            const int k = ok ? i / D : 0, d = ok ? i % D : 0;
-            a[u] = ok ? rsum[i] : 0.f; b[u] = st[k * (D + 1) + d]; c[u] = rs[k];
-        }
-#pragma unroll
-        for (int u = 0; u < FB; ++u) {
-            const int i = i0 + u * blockDim.x;
-            if (i < tot) {
-                const float s = a[u] * decay + one_minus_decay * b[u];
-                rsum[i] = s;
-                const float size_ = (c[u] + eps) / (n + KC * eps) * n;
-                w[i] = s / size_;
-            }
-        }
-    }
-}
-
-// ---- host side of the generic geometry ----------------------------------------------------------------------------------
-static bool vq_instantiated(int D, int KC) { return D == VQ_D && (KC == 512 || KC == 256 || KC == 128); }
 static bool vq_generic_search_ok(int D, int KC) { return D % 16 == 0 && D >= 16 && D <= 256 && KC % 64 == 0 && KC >= 64 && KC <= 2048; }
+
+// set the dynamic-LDS limit (where any is asked for), launch, check
+template <class... P, class... A>
+static int vq_launch(const char *name, void (*kernel)(P...), dim3 grid, int threads, int smem, hipStream_t s, A... args) {
+    if (smem > 0) {
+        const hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        if (e != hipSuccess) { lvt_set_error("%s: cannot get %d B LDS: %s", name, smem, hipGetErrorString(e)); return LVT_ELAUNCH; }
+    }
+    hipLaunchKernelGGL(kernel, grid, dim3(threads), smem, s, args...);
+    LVT_CHECK_LAUNCH(name);
+    return LVT_OK;
+}
+// f(std::integral_constant<int, KC>) for the instantiated codebook sizes
+template <class F>
+static int vq_for_kc(int KC, F &&f) {
+    switch (KC) {
+        case 512: return f(std::integral_constant<int, 512>{});
+        case 256: return f(std::integral_constant<int, 256>{});
+        case 128: return f(std::integral_constant<int, 128>{});
+    }
+    lvt_set_error("vq: codebook size %d not instantiated", KC);
+    return LVT_EINVAL;
+}
+// persistent search grid: one workgroup per CU and group (LDS-bound), capped by the row tiles
+static int vq_persistent_blocks(long long rows, int groups) {
+    const long long need = lvt_cdiv((rows + 31) / 32, VQ_THREADS / 64);
+    const long long b = LVT_NUM_CU / groups < need ? LVT_NUM_CU / groups : need;
+    return b < 1 ? 1 : (int)b;
+}
 
 // workspace of the generic search: nrm, emax, hcb [num][KC] fp32, gsc [num][2], hi, lo [num][KC][D] fp16 (256-byte aligned pieces)
 static size_t vqg_al(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -1442,32 +1367,16 @@ static int vqg_search(const float *z, long long rows, int ldz, int num, int KC, 
                       int P, bool f32, const VqgWs &w, hipStream_t s) {
     constexpr int VQG_THREADS = vqg_threads<DG>();
     const dim3 grid((unsigned)lvt_cdiv(rows, 32 * (VQG_THREADS / 64)), num);
-    hipError_t e;
-    if (f32) {
-        const int smem = 2 * VqgF32<DG>::BUF;
-        e = hipFuncSetAttribute((const void *)lvt_vq_nearest_gen_f32_kernel<DG>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) { lvt_set_error("vq_nearest: cannot get %d B LDS: %s", smem, hipGetErrorString(e)); return LVT_ELAUNCH; }
-        hipLaunchKernelGGL(lvt_vq_nearest_gen_f32_kernel<DG>, grid, dim3(VQG_THREADS), smem, s, z, rows, ldz, KC, codebooks,
-                           (const float *)w.nrm, idx_out, P, num);
-        LVT_CHECK_LAUNCH("lvt_vq_nearest_gen_f32_kernel");
-    } else {
-        const int smem = 2 * VqgF16<DG>::BUF;
-        e = hipFuncSetAttribute((const void *)lvt_vq_nearest_gen_f16x2_kernel<DG>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) { lvt_set_error("vq_nearest: cannot get %d B LDS: %s", smem, hipGetErrorString(e)); return LVT_ELAUNCH; }
-        hipLaunchKernelGGL(lvt_vq_nearest_gen_f16x2_kernel<DG>, grid, dim3(VQG_THREADS), smem, s, z, rows, ldz, KC,
-                           (const unsigned short *)w.hi, (const unsigned short *)w.lo, (const float *)w.hcb,
-                           (const float *)w.gsc, idx_out, P, num);
-        LVT_CHECK_LAUNCH("lvt_vq_nearest_gen_f16x2_kernel");
-    }
-    return LVT_OK;
+    if (f32)
+        return vq_launch("lvt_vq_nearest_gen_f32_kernel", lvt_vq_nearest_gen_f32_kernel<DG>, grid, VQG_THREADS,
+                         2 * VqgF32<DG>::BUF, s, z, rows, ldz, KC, codebooks, w.nrm, idx_out, P, num);
+    return vq_launch("lvt_vq_nearest_gen_f16x2_kernel", lvt_vq_nearest_gen_f16x2_kernel<DG>, grid, VQG_THREADS,
+                     2 * VqgF16<DG>::BUF, s, z, rows, ldz, KC, w.hi, w.lo, w.hcb, w.gsc, idx_out, P, num);
 }
 
+// (arguments validated by lvt_vq_nearest)
 static int vq_nearest_generic(const float *z, long long rows, int ldz, int num, int D, int KC, const float *codebooks,
                               long long *idx_out, int P, int flags, void *workspace, size_t workspace_bytes, hipStream_t s) {
-    LVT_REQUIRE(vq_generic_search_ok(D, KC),
-                "vq_nearest: unsupported geometry D=%d KC=%d (D: multiple of 16 in 16..256; KC: multiple of 64 in 64..2048)", D, KC);
-    LVT_REQUIRE(rows > 0 && num > 0 && P > 0 && rows % P == 0, "vq_nearest: bad rows/P");
-    LVT_REQUIRE(ldz % 4 == 0 && ldz >= num * D && lvt_aligned16(z) && lvt_aligned16(codebooks), "vq_nearest: alignment / ldz");
     const VqgWs w = vqg_ws(workspace, num, D, KC);
     if (!workspace || workspace_bytes < w.bytes || ((uintptr_t)workspace & 255)) {
         lvt_set_error("vq_nearest: the generic search needs a 256-byte aligned workspace of %zu B", w.bytes);
@@ -1495,24 +1404,6 @@ static int vq_nearest_generic(const float *z, long long rows, int ldz, int num, 
     return LVT_EINVAL;
 }
 
-// generic EMA statistics: codes per range and row chunks (~two workgroups per CU over all groups and ranges)
-static void emag_plan(long long rows, int num, int D, int KC, int *kt, long long *rows_per_chunk, int *nchunks) {
-    int k = EMAG_ACC_BYTES / (4 * (D + 1)) / 64 * 64;
-    if (k > KC) k = KC;
-    const int nr = (KC + k - 1) / k;
-    long long target = 2LL * LVT_NUM_CU / ((long long)(num > 0 ? num : 1) * nr);
-    if (target < 1) target = 1;
-    long long rpc = lvt_cdiv(rows, target);
-    rpc = lvt_cdiv(rpc, 64) * 64;
-    if (rpc < 256) rpc = 256;
-    *kt = k;
-    *rows_per_chunk = rpc;
-    *nchunks = (int)lvt_cdiv(rows, rpc);
-}
-
-// ------------------------------------------------------------------------------------------------
-static int vq_smem_bytes(int KC) { return (VQ_D * (KC + 1) + KC) * (int)sizeof(float); }
-
 extern "C" size_t lvt_vq_nearest_workspace_bytes(long long rows, int num, int KC) {
     const int nparts = KC / VQH_CODES > 0 ? KC / VQH_CODES : 1;
     return (size_t)rows * num * nparts * (sizeof(float) + sizeof(int));
@@ -1526,194 +1417,104 @@ extern "C" int lvt_vq_nearest(const float *z, long long rows, int ldz, int num, 
                               const float *codebooks, long long *idx_out, int P, int flags, void *workspace,
                               size_t workspace_bytes, void *stream) {
     LVT_REQUIRE(z && codebooks && idx_out, "vq_nearest: null pointer");
-    if ((flags & LVT_VQ_GENERIC) || !vq_instantiated(D, KC))
-        return vq_nearest_generic(z, rows, ldz, num, D, KC, codebooks, idx_out, P, flags, workspace, workspace_bytes,
-                                  (hipStream_t)stream);
-    LVT_REQUIRE(D == VQ_D, "vq_nearest: only D=%d per codebook is instantiated (got %d)", VQ_D, D);
-    LVT_REQUIRE(KC == 512 || KC == 256 || KC == 128, "vq_nearest: codebook size %d not instantiated", KC);
+    LVT_REQUIRE(vq_generic_search_ok(D, KC),
+                "vq_nearest: unsupported geometry D=%d KC=%d (D: multiple of 16 in 16..256; KC: multiple of 64 in 64..2048)", D, KC);
     LVT_REQUIRE(rows > 0 && num > 0 && P > 0 && rows % P == 0, "vq_nearest: bad rows/P");
-    LVT_REQUIRE(ldz % 4 == 0 && ldz >= num * D && lvt_aligned16(z) && lvt_aligned16(codebooks),
-                "vq_nearest: alignment / ldz");
-    if (!(flags & LVT_MATH_F32) && (flags & LVT_VQ_COARSE)) {
-        const long long need_ = lvt_cdiv((rows + 31) / 32, VQ_THREADS / 64);
-        int bpp = LVT_NUM_CU / num;                     // one workgroup per CU (LDS-bound)
-        if (bpp > need_) bpp = (int)need_;
-        if (bpp < 1) bpp = 1;
-        hipStream_t s = (hipStream_t)stream;
-        if (KC == 512) hipLaunchKernelGGL(lvt_vq_nearest_coarse_kernel<512>, dim3(bpp, num), dim3(VQ_THREADS), 0, s, z, rows, ldz, codebooks, idx_out, P, num);
-        else if (KC == 256) hipLaunchKernelGGL(lvt_vq_nearest_coarse_kernel<256>, dim3(bpp, num), dim3(VQ_THREADS), 0, s, z, rows, ldz, codebooks, idx_out, P, num);
-        else hipLaunchKernelGGL(lvt_vq_nearest_coarse_kernel<128>, dim3(bpp, num), dim3(VQ_THREADS), 0, s, z, rows, ldz, codebooks, idx_out, P, num);
-        LVT_CHECK_LAUNCH("lvt_vq_nearest_coarse_kernel");
-        return LVT_OK;
-    }
-    if ((flags & LVT_MATH_F16X2) && !(flags & LVT_MATH_F32)) {
-        const long long need_ = lvt_cdiv((rows + 31) / 32, VQ_THREADS / 64);
-        int bpp = LVT_NUM_CU / num;                     // one workgroup per CU (LDS-bound)
-        if (bpp > need_) bpp = (int)need_;
-        if (bpp < 1) bpp = 1;
-        hipStream_t s = (hipStream_t)stream;
-        const int smem = 2 * KC * VQF_LD * (int)sizeof(unsigned short) + (KC + 16) * (int)sizeof(float);
-        hipError_t e;
-#define VQF_LAUNCH(KCV)                                                                                                \
-    e = hipFuncSetAttribute((const void *)lvt_vq_nearest_f16x2_kernel<KCV>, hipFuncAttributeMaxDynamicSharedMemorySize, smem); \
-    if (e != hipSuccess) { lvt_set_error("vq_nearest: cannot get %d B LDS: %s", smem, hipGetErrorString(e));           \
-        return LVT_ELAUNCH; }                                                                                          \
-    hipLaunchKernelGGL(lvt_vq_nearest_f16x2_kernel<KCV>, dim3(bpp, num), dim3(VQ_THREADS), smem, s, z, rows, ldz, codebooks, idx_out, P, num);
-        if (KC == 512) { VQF_LAUNCH(512) } else if (KC == 256) { VQF_LAUNCH(256) } else { VQF_LAUNCH(128) }
-#undef VQF_LAUNCH
-        LVT_CHECK_LAUNCH("lvt_vq_nearest_f16x2_kernel");
-        return LVT_OK;
-    }
-    if (!(flags & LVT_MATH_F32) && KC % VQH_CODES == 0 && workspace &&
-        workspace_bytes >= lvt_vq_nearest_workspace_bytes(rows, num, KC)) {
-        const int nparts = KC / VQH_CODES;
-        float *pbest = (float *)workspace;
-        int *pidx = (int *)(pbest + rows * num * nparts);
-        int bpp = LVT_NUM_CU / (num * nparts);        // one workgroup per CU (LDS-bound)
-        const long long need_ = lvt_cdiv((rows + 31) / 32, VQ_THREADS / 64);
-        if (bpp > need_) bpp = (int)need_;
-        if (bpp < 1) bpp = 1;
-        hipLaunchKernelGGL(lvt_vq_nearest_half_kernel, dim3(bpp, nparts, num), dim3(VQ_THREADS), 0, (hipStream_t)stream, z,
-                           rows, ldz, KC, codebooks, pbest, pidx);
-        LVT_CHECK_LAUNCH("lvt_vq_nearest_half_kernel");
-        hipLaunchKernelGGL(lvt_vq_nearest_merge_kernel, dim3((unsigned)lvt_cdiv(rows * num, 256)), dim3(256), 0,
-                           (hipStream_t)stream, (const float *)pbest, (const int *)pidx, rows, num, nparts, P, idx_out);
-        LVT_CHECK_LAUNCH("lvt_vq_nearest_merge_kernel");
-        return LVT_OK;
-    }
-    const long long ntiles = (rows + 31) / 32;
-    int bpg = LVT_NUM_CU / num;                       // one workgroup per CU (LDS-bound)
-    const long long need = lvt_cdiv(ntiles, VQ_THREADS / 64);
-    if (bpg > need) bpg = (int)need;
-    if (bpg < 1) bpg = 1;
-    const int smem = vq_smem_bytes(KC);
+    LVT_REQUIRE(ldz % 4 == 0 && ldz >= num * D && lvt_aligned16(z) && lvt_aligned16(codebooks), "vq_nearest: alignment / ldz");
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e;
-#define VQ_LAUNCH(KCV)                                                                                          \
-    e = hipFuncSetAttribute((const void *)lvt_vq_nearest_kernel<KCV>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                            smem);                                                                              \
-    if (e != hipSuccess) { lvt_set_error("vq_nearest: cannot get %d B LDS: %s", smem, hipGetErrorString(e));    \
-        return LVT_ELAUNCH; }                                                                                   \
-    hipLaunchKernelGGL(lvt_vq_nearest_kernel<KCV>, dim3(bpg * num), dim3(VQ_THREADS), smem, s, z, rows, ldz, num, \
-                       codebooks, idx_out, P, bpg);
-    if (KC == 512) { VQ_LAUNCH(512) } else if (KC == 256) { VQ_LAUNCH(256) } else { VQ_LAUNCH(128) }
-#undef VQ_LAUNCH
-    LVT_CHECK_LAUNCH("lvt_vq_nearest_kernel");
-    return LVT_OK;
+    if ((flags & LVT_VQ_GENERIC) || !vq_route(D, KC).inst)
+        return vq_nearest_generic(z, rows, ldz, num, D, KC, codebooks, idx_out, P, flags, workspace, workspace_bytes, s);
+    return vq_for_kc(KC, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        const int bpg = vq_persistent_blocks(rows, num);
+        if (!(flags & LVT_MATH_F32) && (flags & LVT_VQ_COARSE))
+            return vq_launch("lvt_vq_nearest_coarse_kernel", lvt_vq_nearest_coarse_kernel<K>, dim3(bpg, num), VQ_THREADS, 0, s,
+                             z, rows, ldz, codebooks, idx_out, P, num);
+        if ((flags & LVT_MATH_F16X2) && !(flags & LVT_MATH_F32))
+            return vq_launch("lvt_vq_nearest_f16x2_kernel", lvt_vq_nearest_f16x2_kernel<K>, dim3(bpg, num), VQ_THREADS,
+                             2 * K * VQF_LD * (int)sizeof(unsigned short) + (K + 16) * (int)sizeof(float), s, z, rows, ldz,
+                             codebooks, idx_out, P, num);
+        // bf16x3: half a codebook per workgroup, then a merge pass; without the workspace for it the f32 kernel serves
+        if (!(flags & LVT_MATH_F32) && K % VQH_CODES == 0 && workspace &&
+            workspace_bytes >= lvt_vq_nearest_workspace_bytes(rows, num, K)) {
+            const int nparts = K / VQH_CODES;
+            float *pbest = (float *)workspace;
+            int *pidx = (int *)(pbest + rows * num * nparts);
+            const int rc = vq_launch("lvt_vq_nearest_half_kernel", lvt_vq_nearest_half_kernel,
+                                     dim3(vq_persistent_blocks(rows, num * nparts), nparts, num), VQ_THREADS, 0, s, z, rows, ldz,
+                                     K, codebooks, pbest, pidx);
+            if (rc != LVT_OK) return rc;
+            return vq_launch("lvt_vq_nearest_merge_kernel", lvt_vq_nearest_merge_kernel, dim3((unsigned)lvt_cdiv(rows * num, 256)),
+                             256, 0, s, pbest, pidx, rows, num, nparts, P, idx_out);
+        }
+        return vq_launch("lvt_vq_nearest_kernel", lvt_vq_nearest_kernel<K>, dim3(bpg * num), VQ_THREADS,
+                         (VQ_D * (K + 1) + K) * (int)sizeof(float), s, z, rows, ldz, num, codebooks, idx_out, P, bpg);
+    });
 }
 
 extern "C" int lvt_vq_gather(const long long *idx, const float *codebooks, long long rows, int num, int D, int KC,
                              int P, float *out, int ldo, void *stream) {
-    if (D != VQ_D) {
-        LVT_REQUIRE(idx && codebooks && out && D % 4 == 0 && D > 0 && num > 0 && rows > 0 && P > 0 && rows % P == 0 &&
-                    ldo >= num * D, "vq_gather: bad args");
-        LVT_REQUIRE(ldo % 4 == 0 && lvt_aligned16(out) && lvt_aligned16(codebooks), "vq_gather: out / codebooks must be 16-byte aligned");
-        const long long items = rows * num * (D / 4);
-        const int blocks = (int)(lvt_cdiv(items, 256 * GATHER_UNROLL) < 8192 ? lvt_cdiv(items, 256 * GATHER_UNROLL) : 8192);
-        hipLaunchKernelGGL(lvt_vq_gather_gen_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, idx, codebooks, rows,
-                           num, D, KC, P, out, ldo);
-        LVT_CHECK_LAUNCH("lvt_vq_gather_gen_kernel");
-        return LVT_OK;
-    }
-    LVT_REQUIRE(idx && codebooks && out && D == VQ_D && rows > 0 && rows % P == 0, "vq_gather: bad args");
-    const long long pairs = rows * num;
+    LVT_REQUIRE(idx && codebooks && out && D % 4 == 0 && D > 0 && num > 0 && rows > 0 && P > 0 && rows % P == 0 &&
+                ldo >= num * D, "vq_gather: bad args");
     LVT_REQUIRE(ldo % 4 == 0 && lvt_aligned16(out) && lvt_aligned16(codebooks), "vq_gather: out / codebooks must be 16-byte aligned");
-    const int blocks = (int)(lvt_cdiv(pairs, 16 * GATHER_UNROLL) < 8192 ? lvt_cdiv(pairs, 16 * GATHER_UNROLL) : 8192);
-    hipLaunchKernelGGL(lvt_vq_gather_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, idx, codebooks, rows,
-                       num, KC, P, out, ldo);
-    LVT_CHECK_LAUNCH("lvt_vq_gather_kernel");
-    return LVT_OK;
+    const long long items = rows * num * (D / 4);
+    const int blocks = (int)(lvt_cdiv(items, 256 * GATHER_UNROLL) < 8192 ? lvt_cdiv(items, 256 * GATHER_UNROLL) : 8192);
+    return vq_launch("lvt_vq_gather_kernel", vq_route(D, KC).d64 ? lvt_vq_gather_kernel<VQ_D> : lvt_vq_gather_kernel<0>,
+                     dim3(blocks), 256, 0, (hipStream_t)stream, idx, codebooks, rows, num, D, KC, P, out, ldo);
 }
 
-static void ema_chunks(long long rows, int num, long long *rows_per_chunk, int *nchunks) {
-    long long target = LVT_NUM_CU / (num > 0 ? num : 1);          // ~one workgroup per CU
+// EMA statistics: codes per range (`whole`: the codebook is the one range), rows per chunk and row chunks -- about one
+// workgroup per CU over all groups when a workgroup's accumulator fills the LDS (`whole`), two per CU over all groups and
+// ranges otherwise.  The partial sums are added in chunk order, so the results depend on this plan bit for bit.
+struct EmaPlan { int kt; long long rows_per_chunk; int nchunks; };
+static EmaPlan ema_plan(long long rows, int num, int D, int KC, bool whole) {
+    int kt = whole ? KC : EMAG_ACC_BYTES / (4 * (D + 1)) / 64 * 64;
+    if (kt > KC) kt = KC;
+    const int nr = (KC + kt - 1) / kt;
+    long long target = (whole ? 1LL : 2LL) * LVT_NUM_CU / ((long long)(num > 0 ? num : 1) * nr);
     if (target < 1) target = 1;
     long long rpc = lvt_cdiv(rows, target);
     rpc = lvt_cdiv(rpc, 64) * 64;
     if (rpc < 256) rpc = 256;
-    *rows_per_chunk = rpc;
-    *nchunks = (int)lvt_cdiv(rows, rpc);
+    return {kt, rpc, (int)lvt_cdiv(rows, rpc)};
 }
 extern "C" size_t lvt_vq_ema_workspace_bytes(long long rows, int num, int D, int KC) {
-    long long rpc; int nch;
-    if (!vq_instantiated(D, KC)) {
-        int kt;
-        emag_plan(rows, num, D, KC, &kt, &rpc, &nch);
-        return (size_t)num * nch * KC * (D + 1) * sizeof(float);
-    }
-    ema_chunks(rows, num, &rpc, &nch);
-    return (size_t)num * nch * KC * (D + 1) * sizeof(float);
+    return (size_t)num * ema_plan(rows, num, D, KC, vq_route(D, KC).inst).nchunks * KC * (D + 1) * sizeof(float);
 }
 extern "C" int lvt_vq_ema_accumulate(const long long *idx, const float *z, long long rows, int ldz, int num, int D,
                                      int KC, int P, float *stats, void *workspace, size_t workspace_bytes,
                                      void *stream) {
-    if (!vq_instantiated(D, KC)) {
-        LVT_REQUIRE(idx && z && stats && rows > 0 && num > 0 && P > 0 && rows % P == 0, "vq_ema_accumulate: bad args");
-        LVT_REQUIRE(D % 4 == 0 && D >= 4 && D <= 256 && KC >= 1 && KC <= 2048,
-                    "vq_ema_accumulate: unsupported geometry D=%d KC=%d (D: multiple of 4 up to 256; KC <= 2048)", D, KC);
-        LVT_REQUIRE(ldz % 4 == 0 && ldz >= num * D && lvt_aligned16(z), "vq_ema_accumulate: alignment / ldz");
-        int kt; long long rpc; int nch;
-        emag_plan(rows, num, D, KC, &kt, &rpc, &nch);
-        if (!workspace || workspace_bytes < lvt_vq_ema_workspace_bytes(rows, num, D, KC)) {
-            lvt_set_error("vq_ema_accumulate: workspace too small");
-            return LVT_EWORKSPACE;
-        }
-        hipStream_t s = (hipStream_t)stream;
-        const int smem = (((kt * (D + 1) + 3) & ~3) + EMAG_ROWS * D) * (int)sizeof(float);
-        const hipError_t e = hipFuncSetAttribute((const void *)lvt_vq_ema_partial_gen_kernel,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) { lvt_set_error("vq_ema_accumulate: cannot get %d B LDS: %s", smem, hipGetErrorString(e)); return LVT_ELAUNCH; }
-        hipLaunchKernelGGL(lvt_vq_ema_partial_gen_kernel, dim3(nch * ((KC + kt - 1) / kt), num), dim3(EMA_THREADS), smem, s, idx,
-                           z, rows, ldz, num, D, KC, P, kt, rpc, nch, (float *)workspace);
-        LVT_CHECK_LAUNCH("lvt_vq_ema_partial_gen_kernel");
-        const long long per_group = (long long)KC * (D + 1);
-        hipLaunchKernelGGL(lvt_vq_ema_reduce_kernel, dim3((unsigned)lvt_cdiv(per_group, 256), num), dim3(256), 0, s,
-                           (const float *)workspace, nch, per_group, stats);
-        LVT_CHECK_LAUNCH("lvt_vq_ema_reduce_kernel");
-        return LVT_OK;
-    }
-    LVT_REQUIRE(idx && z && stats && D == VQ_D && rows > 0 && rows % P == 0, "vq_ema_accumulate: bad args");
-    LVT_REQUIRE(KC == 512 || KC == 256 || KC == 128, "vq_ema_accumulate: codebook size %d not instantiated", KC);
-    long long rpc; int nch;
-    ema_chunks(rows, num, &rpc, &nch);
+    LVT_REQUIRE(idx && z && stats && rows > 0 && num > 0 && P > 0 && rows % P == 0, "vq_ema_accumulate: bad args");
+    LVT_REQUIRE(D % 4 == 0 && D >= 4 && D <= 256 && KC >= 1 && KC <= 2048,
+                "vq_ema_accumulate: unsupported geometry D=%d KC=%d (D: multiple of 4 up to 256; KC <= 2048)", D, KC);
+    LVT_REQUIRE(ldz % 4 == 0 && ldz >= num * D && lvt_aligned16(z), "vq_ema_accumulate: alignment / ldz");
+    const bool whole = vq_route(D, KC).inst;
+    const EmaPlan pl = ema_plan(rows, num, D, KC, whole);
     if (!workspace || workspace_bytes < lvt_vq_ema_workspace_bytes(rows, num, D, KC)) {
         lvt_set_error("vq_ema_accumulate: workspace too small");
         return LVT_EWORKSPACE;
     }
     hipStream_t s = (hipStream_t)stream;
-    const int smem = (((KC * (VQ_D + 1) + 3) & ~3) + 64 * VQ_D) * (int)sizeof(float);
-    hipError_t e;
-#define EMA_LAUNCH(KCV)                                                                                          \
-    e = hipFuncSetAttribute((const void *)lvt_vq_ema_partial_kernel<KCV>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                            smem);                                                                               \
-    if (e != hipSuccess) { lvt_set_error("vq_ema_accumulate: cannot get %d B LDS: %s", smem, hipGetErrorString(e)); \
-        return LVT_ELAUNCH; }                                                                                    \
-    hipLaunchKernelGGL(lvt_vq_ema_partial_kernel<KCV>, dim3(num * nch), dim3(EMA_THREADS), smem, s, idx, z, rows, ldz, \
-                       num, P, rpc, nch, (float *)workspace);
-    if (KC == 512) { EMA_LAUNCH(512) } else if (KC == 256) { EMA_LAUNCH(256) } else { EMA_LAUNCH(128) }
-#undef EMA_LAUNCH
-    LVT_CHECK_LAUNCH("lvt_vq_ema_partial_kernel");
+    const int smem = (((pl.kt * (D + 1) + 3) & ~3) + EMA_ROWS * D) * (int)sizeof(float);
+    const dim3 grid(pl.nchunks * ((KC + pl.kt - 1) / pl.kt), num);
+    auto partial = [&](auto kernel) {
+        return vq_launch("lvt_vq_ema_partial_kernel", kernel, grid, EMA_THREADS, smem, s, idx, z, rows, ldz, num, D, KC, P, pl.kt,
+                         pl.rows_per_chunk, pl.nchunks, (float *)workspace);
+    };
+    const int rc = whole ? vq_for_kc(KC, [&](auto kc) { return partial(lvt_vq_ema_partial_kernel<VQ_D, decltype(kc)::value>); })
+                         : partial(lvt_vq_ema_partial_kernel<0, 0>);
+    if (rc != LVT_OK) return rc;
     const long long per_group = (long long)KC * (D + 1);
-    hipLaunchKernelGGL(lvt_vq_ema_reduce_kernel, dim3((unsigned)lvt_cdiv(per_group, 256), num), dim3(256), 0, s,
-                       (const float *)workspace, nch, per_group, stats);
-    LVT_CHECK_LAUNCH("lvt_vq_ema_reduce_kernel");
-    return LVT_OK;
+    return vq_launch("lvt_vq_ema_reduce_kernel", lvt_vq_ema_reduce_kernel, dim3((unsigned)lvt_cdiv(per_group, 256), num), 256, 0, s,
+                     (const float *)workspace, pl.nchunks, per_group, stats);
 }
 
 extern "C" int lvt_vq_ema_finalize(const float *stats, int num, int D, int KC, float decay, float eps,
                                    float *running_size, float *running_sum, float *weight, void *stream) {
     LVT_REQUIRE(stats && running_size && running_sum && weight && num > 0, "vq_ema_finalize: bad args");
+    LVT_REQUIRE(D > 0 && D <= 256 && KC > 0 && KC <= 2048, "vq_ema_finalize: unsupported geometry D=%d KC=%d", D, KC);
     // the reference evaluates (1 - decay) in double precision python and hands it to add_(alpha=...)
     const float omd = (float)(1.0 - (double)decay);
-    if (D != VQ_D) {
-        LVT_REQUIRE(D > 0 && D <= 256 && KC > 0 && KC <= 2048, "vq_ema_finalize: unsupported geometry D=%d KC=%d", D, KC);
-        hipLaunchKernelGGL(lvt_vq_ema_finalize_gen_kernel, dim3(num), dim3(512), 0, (hipStream_t)stream, stats, KC, D, decay,
-                           omd, eps, running_size, running_sum, weight);
-        LVT_CHECK_LAUNCH("lvt_vq_ema_finalize_gen_kernel");
-        return LVT_OK;
-    }
-    hipLaunchKernelGGL(lvt_vq_ema_finalize_kernel, dim3(num), dim3(512), 0, (hipStream_t)stream, stats, KC, decay,
-                       omd, eps, running_size, running_sum, weight);
-    LVT_CHECK_LAUNCH("lvt_vq_ema_finalize_kernel");
-    return LVT_OK;
+    return vq_launch("lvt_vq_ema_finalize_kernel", vq_route(D, KC).d64 ? lvt_vq_ema_finalize_kernel<VQ_D> : lvt_vq_ema_finalize_kernel<0>,
+                     dim3(num), 512, 0, (hipStream_t)stream, stats, KC, D, decay, omd, eps, running_size, running_sum, weight);
 }

@@ -89,8 +89,10 @@ def test_forced_generic_matches_specialised_kernel():
     print("forced generic vs f16x2 kernel: %d sub-margin rows differ" % differ)
 
 
-@pytest.mark.parametrize("Dg,K", [(16, 2048), (32, 1024), (64, 2048), (128, 256), (256, 1024), (64, 512)])
+@pytest.mark.parametrize("Dg,K", [(16, 2048), (32, 1024), (64, 2048), (128, 256), (256, 1024), (64, 512), (64, 128), (64, 1024)])
 def test_generic_gather_exact(Dg, K):
+    """Both instantiations of the gather kernel: the compile-time width 64 at the three codebook sizes that route the search
+    and the statistics differently (512, 128: whole-codebook kernels; 1024, 2048: generic), and run-time widths."""
     from lvt_amd.hip import vq
     torch.manual_seed(Dg + K)
     n, num, P = 5, 3, 48
@@ -101,12 +103,29 @@ def test_generic_gather_exact(Dg, K):
     assert torch.equal(out, ref.reshape(n * P, num * Dg))
 
 
-@pytest.mark.parametrize("Dg,K", [(16, 2048), (32, 1024), (64, 2048), (64, 1024), (128, 256), (256, 1024), (256, 64)])
+EMA_GEOMETRIES = [(16, 2048), (32, 1024), (64, 2048), (64, 1024), (128, 256), (256, 1024), (256, 64), (64, 128), (64, 256), (64, 512)]
+
+
+@pytest.mark.parametrize("Dg,K", EMA_GEOMETRIES)
 def test_generic_ema_accumulate(Dg, K):
-    """Counts exact, sums within 1e-6 relative of a float64 index_add_, two runs bit-identical (skewed code histogram)."""
+    """Counts exact, sums within 1e-6 relative of a float64 index_add_, two runs bit-identical (skewed code histogram).
+    (64, 128 | 256 | 512) is the whole-codebook family of the statistics kernel, the rest the ranged one (width 16: threads with
+    nothing to stage; width 256: all eight staging registers)."""
+    _check_ema_accumulate(Dg, K, 24, 256)
+
+
+@pytest.mark.parametrize("n,P", [(5, 48), (1, 48)])
+@pytest.mark.parametrize("Dg,K", EMA_GEOMETRIES)
+def test_generic_ema_accumulate_few_rows(Dg, K, n, P):
+    """As test_generic_ema_accumulate on 240 rows (below the 256-row chunk floor, the last tile 48 rows) and on 48 rows (less
+    than one 64-row tile)."""
+    _check_ema_accumulate(Dg, K, n, P)
+
+
+def _check_ema_accumulate(Dg, K, n, P):
     from lvt_amd.hip import vq
     torch.manual_seed(Dg * K)
-    n, num, P = 24, 3, 256
+    num = 3
     rows = n * P
     z = torch.randn(rows, num * Dg)
     idx = torch.randint(0, K, (n, num, P))
@@ -121,6 +140,29 @@ def test_generic_ema_accumulate(Dg, K):
         tot = torch.zeros(K, Dg, dtype=torch.float64).index_add_(0, flat, z[:, Dg * g:Dg * (g + 1)].double())
         assert torch.equal(s1[g, :, Dg].double(), cnt), g
         assert rel_err(s1[g, :, :Dg], tot) < 1e-6, g
+
+
+@pytest.mark.parametrize("num,K,D", [(3, 128, 64), (2, 64, 16), (1, 2048, 256)])
+def test_ema_finalize_against_fp64(num, K, D):
+    """vq.ema_finalize (both instantiations: compile-time width 64, run-time width) against the reference's update
+    (vq_embedding.py:48-59) in float64: decay-lerp of running_size and running_sum, Laplace-smoothed sizes, new codebook."""
+    from lvt_amd.hip import vq
+    torch.manual_seed(num * K + D)
+    decay, eps = 0.99, 1e-5
+    rs = torch.rand(num, K) * 4 + 0.1
+    rsum = torch.randn(num, K, D)
+    stats = torch.randn(num, K, D + 1)
+    stats[:, :, D] = torch.randint(0, 40, (num, K)).float()        # counts
+    rs_d, rsum_d, w_d = rs.to(DEV), rsum.to(DEV), torch.zeros(num, K, D, device=DEV)
+    vq.ema_finalize(stats.to(DEV), rs_d, rsum_d, w_d, decay=decay, eps=eps)
+    rs64 = rs.double() * decay + (1 - decay) * stats[:, :, D].double()
+    rsum64 = rsum.double() * decay + (1 - decay) * stats[:, :, :D].double()
+    n = rs64.sum(1, keepdim=True)
+    size_ = (rs64 + eps) / (n + K * eps) * n
+    for g in range(num):
+        assert rel_err(rs_d[g], rs64[g]) < 1e-5, g
+        assert rel_err(rsum_d[g], rsum64[g]) < 1e-5, g
+        assert rel_err(w_d[g], rsum64[g] / size_[g].unsqueeze(1)) < 1e-5, g
 
 
 @pytest.mark.parametrize("num,K,D", [(8, 1024, 256), (2, 256, 256), (4, 2048, 256)])

@@ -251,6 +251,20 @@ def test_frame_resident_kernel_routing_of_the_vqvae_layers():
     assert lib.lvt_conv3d_bwd_weight_workspace_bytes(ctypes.byref(k3)) >= 32 * 9 * 256 * 256 * 4
 
 
+def test_vq_ema_statistics_plan_is_the_recorded_one():
+    """lvt_vq_ema_workspace_bytes (launches nothing: no GPU needed) = num x row chunks x KC x (D + 1) floats, so it shows the
+    row chunking of the EMA statistics.  The chunk partials are summed in chunk order: a planner that returns another chunk
+    count changes the bits of the codebook update.  Constants recorded from the library before the whole-codebook and the
+    ranged planner were merged: (rows, num, D, KC) on the whole-codebook family (one workgroup per CU), on the ranged one
+    (two per CU over groups and code ranges), below the 256-row chunk floor and below one 64-row tile."""
+    from lvt_amd.hip import binding as L
+    lib = L.lib()
+    recorded = {(131072, 4, 64, 512): 34078720, (240, 3, 64, 128): 99840, (6144, 3, 64, 1024): 19169280,
+                (6144, 3, 256, 64): 4737024, (48, 1, 16, 2048): 139264}
+    for args, nbytes in recorded.items():
+        assert lib.lvt_vq_ema_workspace_bytes(*args) == nbytes, args
+
+
 def test_bench_generation_roofline_arithmetic_is_integer():
     """Rounds 2 and 3 lost five GPU boxes to one line of bench.py: `hd = v.N_HEAD_D * v.DA` with N_HEAD_D a per-layer
     tuple made the K/V byte count an `int * tuple` -- a request for a 4.5e12-element tuple (36 TB) that exhausted the host.
