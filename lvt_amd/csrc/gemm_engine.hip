@@ -80,7 +80,8 @@ __device__ __forceinline__ void split3(const float4 v, uint2 &p1, uint2 &p2, uin
 // Staged-row placement of the bf16 planes.  128-row tiles are stored "4x32 transposed" (logical row m lives at
 // physical row (m & 3) * 32 + (m >> 2)) with 64 pad bytes after every 32 physical rows: the 16-byte MFMA operand
 // reads and the 8-byte stores of the k-contiguous loaders are bank-conflict free, the 8-byte stores of the
-// m-contiguous loaders (4 consecutive rows per lane) are 2-way.  Narrow (32-row) tiles keep the identity order.
+// m-contiguous loaders of lvt_gemm_kernel (4 consecutive rows per lane) are 2-way.  Narrow (32-row) tiles keep the identity
+// order.  (lvt_gemm_wide_kernel does not put its m-contiguous operands into this image: WT_PA / WT_PB below.)
 template <int ROWS> __device__ __forceinline__ int hrow(int m) {
     if (ROWS >= 128) {
         const int r = (m & ~127) + ((m & 3) << 5) + ((m & 127) >> 2);
@@ -1494,17 +1495,45 @@ __global__ __launch_bounds__(PT_THREADS) void lvt_conv_patch_kernel(const KParam
 //     the stores of tile k+1 are independent of the MFMA block of tile k and share its issue window, and there is ONE
 //     barrier per k-tile;
 //   * the global loads of tile k+2 are issued as soon as the registers of tile k+1 have been split: a full iteration of
-//     latency cover.
+//     latency cover;
+//   * an operand that is contiguous along m / n (A of the TN form, B of the NN and TN forms) is NOT transposed on its way
+//     into LDS (round 7): each fetched float4 (4 consecutive m at one k) is split as it stands and leaves as one 8-byte store
+//     per plane into a [32 k][m] image in memory order, and the MFMA fragments (8 consecutive k of one m) come out of it
+//     through two ds_read_b64_tr_b16 each -- the same fp16 bits in the same MFMA order as the k-contiguous image with
+//     ds_read_b128 (tests/test_gpu_wide_gemm_tr.py: bit-equal to the NT form).  The B tile is fetched by all 512 threads,
+//     two float4 each.  Before: a 4 x 4 register transpose per thread, 2-way conflicted stores, and B staged by half the
+//     workgroup -- TN 91.6 -> 84.6 us, NN 84.6 -> 82.9 us per launch in the DSFVT step
+//     (profiles/r07_wide_gemm_tr_loader.txt).
 // Serves the plain forms (NT / NN / TN incl. 2-level k, batches, split-K with column sums); everything else and the other
 // arithmetic modes stay on lvt_gemm_kernel.
 // ------------------------------------------------------------------------------------------------
 #define WIDE_THREADS 512
+// m-contiguous operand tiles: [32 k rows][256 or 128 columns] fp16 per plane, in memory order.  Row pitch = 16 dwords mod 64:
+// the four k rows of one transposing read (16 columns = 8 dwords each, two 16-lane groups per 32-lane half) fall on four
+// disjoint 16-bank ranges, and a staging store (16 lanes x 8 B contiguous) covers the 32 store banks once.
+#define WT_PA (256 + 32)                 // 576 B
+#define WT_PB (128 + 32)                 // 320 B
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+// 8 consecutive k (4 + 4 image rows) of the lane's column: two ds_read_b64_tr_b16.  Lane 4q + p of a 16-lane group passes the
+// address of row q, columns 4p .. 4p+3 of the group's [4][16] block and receives column (lane & 15), rows 0..3.  Every
+// address is a multiple of 8 bytes and EXEC is all ones wherever this is called (conv_wgrad.hip: wg_frag).
+__device__ __forceinline__ f16x8 wide_tr_frag(const unsigned short *p, int pitch4) {
+    typedef __attribute__((address_space(3))) s16x4 lds_v4;
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4 *)(p));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4 *)(p + pitch4));
+    union { struct { s16x4 a, b; } s; f16x8 v; } u;
+    u.s.a = lo; u.s.b = hi;
+    return u.v;
+}
 template <int TA, int TB>
 __global__ __launch_bounds__(WIDE_THREADS, 2) void lvt_gemm_wide_kernel(const KParams p) {
     constexpr int BM = 256, BN = 128, WM = 4, WN = 2, TM = 2, TN = 2;
     constexpr int AMODE = TA ? A_MPLAIN : A_KPLAIN;
-    constexpr int PSA = HPlane<BM>::SIZE, PSB = HPlane<BN>::SIZE;
+    constexpr int PA = WT_PA, PB = WT_PB;
+    constexpr int PSA = TA ? BK * PA : HPlane<BM>::SIZE, PSB = TB ? BK * PB : HPlane<BN>::SIZE;
     constexpr int STAGE = 2 * (PSA + PSB);                                  // fp16 elements per buffer
+    static_assert(PA % 4 == 0 && PB % 4 == 0 && PSA % 8 == 0 && PSB % 8 == 0, "transposing reads need 8-byte aligned addresses");
+    static_assert(BK * PA <= HPlane<BM>::SIZE && BK * PB <= HPlane<BN>::SIZE, "the memory-order images are the smaller ones");
     constexpr int STAGE_FLOATS = (2 * STAGE) / 2 + 8;
     constexpr int TURN_FLOATS = WM * WN * 32 * (TN * 32);
     constexpr int LDS_FLOATS = STAGE_FLOATS > TURN_FLOATS ? STAGE_FLOATS : TURN_FLOATS;
@@ -1524,16 +1553,15 @@ __global__ __launch_bounds__(WIDE_THREADS, 2) void lvt_gemm_wide_kernel(const KP
     // The main loop carries NO bounds checks (one basic block: the split of tile k+1 and the loads of tile k+2 interleave
     // with the MFMAs of tile k): rows / columns beyond M / N are fetched from a clamped, valid address -- they only feed
     // output rows / columns that the epilogue does not store -- and the launcher sends K % 32 != 0 to lvt_gemm_kernel.
-    float4 av[4], bv[TB ? 4 : 2];
+    float4 av[4], bv[2];
     const int r0 = tid >> 3, kq = tid & 7;            // k-contiguous
     const int kk0 = TA ? tid >> 6 : 0, mq = tid & 63; // A m-contiguous: 8 k groups x 64 m quads
-    const int bkk0 = (tid >> 5) & 7, bnq = tid & 31;  // B n-contiguous: 8 k groups x 32 n quads (threads 0..255)
-    const bool bact = !TB || tid < 256;
+    const int bkk0 = tid >> 5, bnq = tid & 31;        // B n-contiguous: 16 k row pairs x 32 n quads
     // Addresses = a workgroup-uniform base that walks k (scalar registers, scalar arithmetic) + per-thread BYTE offsets that
     // never change (the launcher keeps every operand below 4 GB per batch): the loop has no vector address arithmetic --
     // 43 of its 115 VALU instructions before this.
     const char *Ak = reinterpret_cast<const char *>(tc.A), *Bk = reinterpret_cast<const char *>(tc.B);
-    unsigned aoff[4], boff_g[TB ? 4 : 2];
+    unsigned aoff[4], boff_g[2];
     int a_kin = 0, b_kin = 0;                           // position of the tile inside its k block (2-level k), uniform
     if (!TA) {
 #pragma unroll
@@ -1556,7 +1584,7 @@ __global__ __launch_bounds__(WIDE_THREADS, 2) void lvt_gemm_wide_kernel(const KP
     } else {
         const int n = n0 + bnq * 4;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) boff_g[i] = (unsigned)(((long long)(bkk0 * 4 + i) * p.ldb + (n < p.N ? n : 0)) * 4);
+        for (int i = 0; i < 2; ++i) boff_g[i] = (unsigned)(((long long)(bkk0 * 2 + i) * p.ldb + (n < p.N ? n : 0)) * 4);
         Bk += (long long)kbeg * p.ldb * 4;
     }
     const bool sum_on = TA && p.colsum_partial != nullptr && n0 == 0;
@@ -1584,10 +1612,8 @@ __global__ __launch_bounds__(WIDE_THREADS, 2) void lvt_gemm_wide_kernel(const KP
             Bk += wrap ? ((long long)p.b_skb - p.b_kb + BK) * 4 : (long long)BK * 4;
             b_kin = wrap ? 0 : b_kin;
         } else {
-            if (bact) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) bv[i] = *reinterpret_cast<const float4 *>(Bk + boff_g[i]);
-            }
+            for (int i = 0; i < 2; ++i) bv[i] = *reinterpret_cast<const float4 *>(Bk + boff_g[i]);
             Bk += (long long)BK * p.ldb * 4;
         }
     };
@@ -1597,13 +1623,27 @@ __global__ __launch_bounds__(WIDE_THREADS, 2) void lvt_gemm_wide_kernel(const KP
 #pragma unroll
             for (int i = 0; i < 4; ++i) store_split2_k<BM>(Ah, r0 + 64 * i, kq * 4, av[i], sa);
         } else {
-            store_split2_block<BM>(Ah, mq * 4, kk0 * 4, av, sa);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                uint2 ph, pl;
+                split2(av[i], sa, ph, pl);
+                unsigned short *d = Ah + (kk0 * 4 + i) * PA + mq * 4;
+                *reinterpret_cast<uint2 *>(d) = ph;
+                *reinterpret_cast<uint2 *>(d + PSA) = pl;
+            }
         }
         if (!TB) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) store_split2_k<BN>(Bh, r0 + 64 * i, kq * 4, bv[i], sb);
-        } else if (bact) {
-            store_split2_block<BN>(Bh, bnq * 4, bkk0 * 4, bv, sb);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                uint2 ph, pl;
+                split2(bv[i], sb, ph, pl);
+                unsigned short *d = Bh + (bkk0 * 2 + i) * PB + bnq * 4;
+                *reinterpret_cast<uint2 *>(d) = ph;
+                *reinterpret_cast<uint2 *>(d + PSB) = pl;
+            }
         }
     };
 
@@ -1615,11 +1655,15 @@ __global__ __launch_bounds__(WIDE_THREADS, 2) void lvt_gemm_wide_kernel(const KP
 #pragma unroll
             for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; acx[i][j][r] = 0.f; }
 
-    int fa[TM], fb[TN];                     // LDS offsets of this lane's operand fragments
+    // LDS offsets of this lane's operand fragments.  k-contiguous image: row l31, k 8 half .. +7 (one ds_read_b128).  Memory-order
+    // image: the lane's address in the transposing read of k rows 8 half .. +3 for the 16 columns its 16-lane group receives.
+    const int trow = 8 * half + ((lane & 15) >> 2), tcol = (lane & 16) + 4 * (lane & 3);
+    int fa[TM], fb[TN];
 #pragma unroll
-    for (int i = 0; i < TM; ++i) fa[i] = hrow<BM>(wm * (TM * 32) + i * 32 + l31) + 8 * half;
+    for (int i = 0; i < TM; ++i) fa[i] = TA ? trow * PA + wm * (TM * 32) + i * 32 + tcol : hrow<BM>(wm * (TM * 32) + i * 32 + l31) + 8 * half;
 #pragma unroll
-    for (int j = 0; j < TN; ++j) fb[j] = 2 * PSA + hrow<BN>(wn * (TN * 32) + j * 32 + l31) + 8 * half;
+    for (int j = 0; j < TN; ++j)
+        fb[j] = 2 * PSA + (TB ? trow * PB + wn * (TN * 32) + j * 32 + tcol : hrow<BN>(wn * (TN * 32) + j * 32 + l31) + 8 * half);
 
     // one k-tile: the MFMA block on buffer `cur`; with STORE the registers (tile kt+1) are split into the other buffer, with
     // FETCH the loads of tile kt+2 follow -- no dependence on the MFMAs: one basic block that the scheduler interleaves
@@ -1633,9 +1677,15 @@ __global__ __launch_bounds__(WIDE_THREADS, 2) void lvt_gemm_wide_kernel(const KP
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
 #pragma unroll
-                for (int i = 0; i < TM; ++i) a[q][i] = *reinterpret_cast<const f16x8 *>(cur + fa[i] + q * PSA + ks);
+                for (int i = 0; i < TM; ++i) {
+                    if constexpr (TA) a[q][i] = wide_tr_frag(cur + fa[i] + q * PSA + ks * PA, 4 * PA);
+                    else a[q][i] = *reinterpret_cast<const f16x8 *>(cur + fa[i] + q * PSA + ks);
+                }
 #pragma unroll
-                for (int j = 0; j < TN; ++j) b[q][j] = *reinterpret_cast<const f16x8 *>(cur + fb[j] + q * PSB + ks);
+                for (int j = 0; j < TN; ++j) {
+                    if constexpr (TB) b[q][j] = wide_tr_frag(cur + fb[j] + q * PSB + ks * PB, 4 * PB);
+                    else b[q][j] = *reinterpret_cast<const f16x8 *>(cur + fb[j] + q * PSB + ks);
+                }
             }
 #pragma unroll
             for (int i = 0; i < TM; ++i)
