@@ -140,7 +140,9 @@ typedef struct {
      * weight gradients of the same shape run as ONE launch with sA_i = A1 - A0 etc. (half the k ranges, twice as long). */
     float *a_colsum;
     long long c_plane;                  /* LVT_EPI_PLANES: distance between the bf16 planes of C (elements)                 */
-    const float *a_amax, *b_amax;       /* LVT_MATH_F16X2: device scalars >= max |A|, max |B| (required in that mode)        */
+    const float *a_amax, *b_amax;       /* LVT_MATH_F16X2: device scalars (required in that mode): any finite value >= max |A|
+                                         * resp. max |B|, 0 included; a product with a zero operand is exactly 0.  An operand
+                                         * with a max below 2^-102 keeps fewer than 27 spare binades          */
     const float *a_amax2, *b_amax2;     /* optional second bounds: the operand scale comes from max(*x_amax, *x_amax2) -- for
                                          * operands that span two tensors (batch strides = address differences)           */
     float *c_amax;                      /* optional, any mode: max |C| is folded into *c_amax (see lvt_amax_io)              */

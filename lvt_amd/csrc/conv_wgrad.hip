@@ -95,14 +95,7 @@ __device__ __forceinline__ void wg_split2(const float4 v, const float s, uint2 &
     wg_split_pair(v.x, v.y, s, ph.x, pl.x);
     wg_split_pair(v.z, v.w, s, ph.y, pl.y);
 }
-__device__ __forceinline__ float wg_f16_scale(const float *amax, int &unscale) {     // = lvt_f16_scale (gemm_engine.hip)
-    if (!amax) return 1.f;
-    const int eb = (int)((__float_as_uint(*amax) >> 23) & 0xffu);
-    int se = 268 - eb;
-    se = se < 2 ? 2 : (se > 252 ? 252 : se);
-    unscale -= se - 127;
-    return __uint_as_float((unsigned)se << 23);
-}
+__device__ __forceinline__ float wg_f16_scale(const float *amax, int &unscale) { return lvt_f16_scale(amax, unscale); }    // lvt_common.h
 // 8 reduction rows (4 + 4) of the lane's column: two transposing reads, `pitch4` = 4 rows further (bf16 elements)
 __device__ __forceinline__ bf16x8 wg_frag(const unsigned short *p, int pitch4) {
     typedef __attribute__((address_space(3))) s16x4 lds_v4;

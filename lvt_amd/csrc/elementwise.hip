@@ -327,11 +327,9 @@ __global__ void lvt_layernorm_fwd_kernel(const float *__restrict__ x, long long 
     float am = 0.f;
     float ps = 1.f;
     if (P2) {
-        // scale of the image: lvt_f16_scale (gemm_engine.hip) of the bound that block 0 stores below
-        const int eb = (int)((__float_as_uint(ln_bound(w_amax, b_amax, d)) >> 23) & 0xffu);
-        int se = 268 - eb;
-        se = se < 2 ? 2 : (se > 252 ? 252 : se);
-        ps = __uint_as_float((unsigned)se << 23);
+        // scale of the image: lvt_f16_scale (lvt_common.h) of the bound that block 0 stores below
+        int un = 0;
+        ps = lvt_f16_scale_bits(__float_as_uint(ln_bound(w_amax, b_amax, d)), un);
     }
     if (y_amax && w_amax) {
         // a-priori bound instead of a reduction: |(x - mean) rstd| <= sqrt(d - 1) on every row, so

@@ -169,18 +169,7 @@ __device__ __forceinline__ void split2_lean(const float4 v, const float s, uint2
     pl.x = f16_pair_mix(f16_mix_lo(ph.x, -1.f, v.x * s), f16_mix_hi(ph.x, -1.f, v.y * s), 2048.f);
     pl.y = f16_pair_mix(f16_mix_lo(ph.y, -1.f, v.z * s), f16_mix_hi(ph.y, -1.f, v.w * s), 2048.f);
 }
-// power-of-two scale of an operand from its max |a| (a device scalar; any upper bound works, a loose one costs range):
-// returns s = 2^e with max * s in [2^14, 2^15) and adds -e to `unscale` (the exponent that undoes it on the result).
-__device__ __forceinline__ float lvt_f16_scale(const float *amax, int &unscale, const float *amax2 = nullptr) {
-    if (!amax) return 1.f;
-    unsigned bits = __float_as_uint(*amax);
-    if (amax2) bits = max(bits, __float_as_uint(*amax2));                            // non-negative floats order like their bits
-    const int eb = (int)((bits >> 23) & 0xffu);                                      // biased exponent (255: inf / nan propagate)
-    int se = 268 - eb;                                                               // 127 + 14 - (eb - 127)
-    se = se < 2 ? 2 : (se > 252 ? 252 : se);
-    unscale -= se - 127;
-    return __uint_as_float((unsigned)se << 23);
-}
+// (the operand scale s: lvt_f16_scale, lvt_common.h -- its upper clamp keeps s * 2048 of f16_split_pair finite)
 template <int ROWS, int LEAN = 0> __device__ __forceinline__ void store_split2_k(unsigned short *lds, int row, int k4, const float4 v, float s) {
     uint2 ph, pl;
     if (LEAN) split2_lean(v, s, ph, pl);

@@ -85,12 +85,7 @@ __device__ __forceinline__ void p2_split4(const float4 v, const float s, uint2 &
     p2_split_pair(v.z, v.w, s, ph.y, pl.y);
 }
 __device__ __forceinline__ float p2_scale(const float *amax, int &unscale) {
-    unsigned bits = __float_as_uint(*amax);
-    const int eb = (int)((bits >> 23) & 0xffu);
-    int se = 268 - eb;
-    se = se < 2 ? 2 : (se > 252 ? 252 : se);
-    unscale -= se - 127;
-    return __uint_as_float((unsigned)se << 23);
+    return lvt_f16_scale_bits(__float_as_uint(*amax), unscale);                      // (lvt_common.h; amax is never NULL here)
 }
 
 // ---- the kernel ----------------------------------------------------------------------------------------------------------

@@ -67,4 +67,26 @@ __device__ __forceinline__ void lvt_block_amax_commit(float m, float *dst, float
             atomicMax(reinterpret_cast<unsigned *>(dst), bits);
     }
 }
+// ---- operand scale of the f16x2 arithmetic (gemm_engine.hip describes the split) -- the ONE definition, restated in Python
+// by tests/util_f16_scale.py.  `bits`: the bit pattern of a non-negative float >= max |a| (0 and subnormals included; 255 in
+// the exponent: inf / nan propagate).  Returns s = 2^(se - 127) with max * s in [2^14, 2^15) wherever the clamp does not bind
+// and adds -(se - 127) to `unscale`, the exponent that undoes it on the result.  Lower clamp 2: s stays a normal number for
+// a max up to 2^127.  Upper clamp 243 = 254 - 11: the splits form v * (s * 2048) for the low term, and s * 2048 must stay
+// finite (<= 2^127) -- with s = 2^125 (the clamp this replaced, 252) it was +inf for every operand with max |a| < 2^-102, and
+// 0 * inf = NaN for an all-zero one.  An operand below 2^-102 therefore sits lower in the fp16 range (max * s = 2^14 for a
+// max of 2^-102, 2^-10 for 2^-126) and has that many fewer spare binades below its max; a zero operand gives exact zeros.
+__device__ __forceinline__ float lvt_f16_scale_bits(unsigned bits, int &unscale) {
+    const int eb = (int)((bits >> 23) & 0xffu);                                      // biased exponent
+    int se = 268 - eb;                                                               // 127 + 14 - (eb - 127)
+    se = se < 2 ? 2 : (se > 243 ? 243 : se);
+    unscale -= se - 127;
+    return __uint_as_float((unsigned)se << 23);
+}
+// from the device scalar(s) that hold the max (any upper bound works, a loose one costs range); NULL: the operand is unscaled
+__device__ __forceinline__ float lvt_f16_scale(const float *amax, int &unscale, const float *amax2 = nullptr) {
+    if (!amax) return 1.f;
+    unsigned bits = __float_as_uint(*amax);
+    if (amax2) bits = max(bits, __float_as_uint(*amax2));                            // non-negative floats order like their bits
+    return lvt_f16_scale_bits(bits, unscale);
+}
 #endif

@@ -186,12 +186,8 @@ __device__ __forceinline__ void tm_split4(const float4 v, float s, unsigned shor
     *reinterpret_cast<uint2 *>(hi) = ph;
     *reinterpret_cast<uint2 *>(lo) = pl;
 }
-__device__ __forceinline__ float tm_scale(const float *amax, int &unscale) {       // = lvt_f16_scale (gemm_engine.hip)
-    const int eb = (int)((__float_as_uint(*amax) >> 23) & 0xffu);
-    int se = 268 - eb;
-    se = se < 2 ? 2 : (se > 252 ? 252 : se);
-    unscale -= se - 127;
-    return __uint_as_float((unsigned)se << 23);
+__device__ __forceinline__ float tm_scale(const float *amax, int &unscale) {       // (lvt_common.h; amax is never NULL here)
+    return lvt_f16_scale_bits(__float_as_uint(*amax), unscale);
 }
 
 __global__ __launch_bounds__(TM_THREADS) void lvt_convt4_mfma_kernel(const float *__restrict__ x, const float *__restrict__ w,

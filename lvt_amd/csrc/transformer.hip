@@ -219,14 +219,15 @@ extern "C" int lvt_attn_softmax_bwd(const float *P, float *dP, int B, int H, int
                                     int bw, float *G, float *ddt, float *ddh, float *ddw, void *stream) {
     LVT_REQUIRE(P && dP && G && ddt && ddh && ddw && B > 0 && H > 0, "attn_softmax_bwd: bad args");
     LVT_REQUIRE(S == bt * bh * bw && S % 256 == 0 && S <= 256 * SM_MAXC, "attn_softmax_bwd: S=%d unsupported", S);
+    // (every argument is judged before the first launch: that launch overwrites dP)
+    const int per_h = (2 * bt - 1) + (2 * bh - 1) + (2 * bw - 1);
+    LVT_REQUIRE(per_h <= 64 && S <= 1024 && (bh * bw) % 4 == 0, "attn_softmax_bwd: %d bank entries per head (max 64)", per_h);
     hipStream_t s = (hipStream_t)stream;
     const long long rows = (long long)H * S;
     hipLaunchKernelGGL(lvt_attn_softmax_bwd_kernel, dim3((unsigned)lvt_cdiv(rows, 4)), dim3(256), 0, s, P, dP, B, H, S,
                        temper, G);
     LVT_CHECK_LAUNCH("lvt_attn_softmax_bwd_kernel");
     BiasGeom g = {bt, bh, bw};
-    const int per_h = (2 * bt - 1) + (2 * bh - 1) + (2 * bw - 1);
-    LVT_REQUIRE(per_h <= 64 && S <= 1024 && (bh * bw) % 4 == 0, "attn_softmax_bwd: %d bank entries per head (max 64)", per_h);
     hipLaunchKernelGGL(lvt_attn_bank_grad_kernel, dim3(H), dim3(64 * BG_WAVES), 0, s, G, H, S, g, ddt, ddh, ddw);
     LVT_CHECK_LAUNCH("lvt_attn_bank_grad_kernel");
     return LVT_OK;
@@ -579,6 +580,7 @@ extern "C" int lvt_xent_fwd(const float *logits, const long long *target, long l
     float *psum = (float *)workspace, *pcnt = psum + XE_BLOCKS;
     hipLaunchKernelGGL(lvt_xent_partial_kernel, dim3(pb), dim3(256), 0, s, row_loss, target, tstride_b, tstride_pos, P,
                        rows, ignore, psum, pcnt);
+    LVT_CHECK_LAUNCH("lvt_xent_partial_kernel");
     hipLaunchKernelGGL(lvt_xent_finish_kernel, dim3(1), dim3(256), 0, s, psum, pcnt, pb, scale, loss, count);
     LVT_CHECK_LAUNCH("lvt_xent_finish_kernel");
     return LVT_OK;

@@ -9,6 +9,8 @@ import os
 import pytest
 import torch
 
+from util_f16_scale import _image_ref, _scale_of  # noqa: F401  (the split and its clamp constant, written once)
+
 pytestmark = pytest.mark.gpu
 
 
@@ -28,24 +30,6 @@ def _dev():
 def _rand(*shape, seed=0, scale=1.0):
     g = torch.Generator().manual_seed(seed + sum(shape))
     return ((torch.rand(*shape, generator=g) * 2 - 1) * scale).to(_dev())
-
-
-def _scale_of(amax):
-    """lvt_f16_scale: the power of two s with amax * s in [2^14, 2^15)."""
-    bits = int(torch.tensor([float(amax)], dtype=torch.float32).view(torch.int32))
-    eb = (bits >> 23) & 0xff
-    se = min(max(268 - eb, 2), 252)
-    return float(torch.tensor([se << 23], dtype=torch.int32).view(torch.float32))
-
-
-def _image_ref(x, amax):
-    """(rows, K) fp32 -> (rows, K / 32, 2, 32) fp16: the P2 image, restated with torch ops."""
-    s = _scale_of(amax)
-    xs = x.double() * s                                   # exact: a power of two
-    hi = xs.float().to(torch.float16)
-    lo = ((xs - hi.double()) * 2048.0).float().to(torch.float16)
-    r, k = x.shape
-    return torch.stack([hi.view(r, k // 32, 32), lo.view(r, k // 32, 32)], dim=2)
 
 
 def _image_view(img):
@@ -80,6 +64,59 @@ def test_p2_pack_ladder_and_zero():
     x[7] = 0
     img = _pack(x)
     assert torch.equal(_image_view(img.data), _image_ref(x, float(x.abs().max())))
+
+
+# ---- the scale's whole range: operands whose max is zero, tiny (both sides of 2^-102, where s * 2048 used to overflow) or huge
+DEGENERATE = {"zero": None, "t126": -126, "t110": -110, "t103": -103, "t101": -101, "huge": 126}
+F32_MIN_NORMAL = 2.0 ** -126
+
+
+def _degenerate(shape, cls, seed):
+    """uniform [-1, 1) times 2^e (exact), or all zero; built on the CPU so that no device pass can flush it first."""
+    g = torch.Generator().manual_seed(seed + sum(shape))
+    u = torch.rand(*shape, generator=g) * 2 - 1
+    e = DEGENERATE[cls]
+    return torch.zeros(*shape) if e is None else torch.ldexp(u, torch.tensor(e))
+
+
+def _check_degenerate_image(xc, img, transpose, cls):
+    """image == restatement under the scale of the record the image was made with; that record is the true max (t126: every
+    element is fp32-subnormal and may be flushed -- by the max pass too -- so those are only required to come out finite)."""
+    rec, true_max = float(img.amax), float(xc.abs().max())
+    if cls == "t126":
+        assert 0.0 <= rec <= true_max
+    else:
+        assert rec == true_max
+    src = xc.t().contiguous() if transpose else xc
+    got, ref = _image_view(img.data).cpu(), _image_ref(src, rec)
+    assert bool(torch.isfinite(got.float()).all())
+    normal = (src.abs() >= F32_MIN_NORMAL) | (src == 0)
+    r, k = src.shape
+    normal = normal.view(r, k // 32, 1, 32).expand(r, k // 32, 2, 32)
+    assert torch.equal(got.view(torch.int16)[normal], ref.view(torch.int16)[normal])
+    if cls == "zero":
+        assert not bool(got.view(torch.int16).any())
+
+
+@pytest.mark.parametrize("cls", list(DEGENERATE))
+@pytest.mark.parametrize("rows,K,transpose", [(64, 64, False), (100, 96, False), (64, 64, True), (100, 96, True)])
+def test_p2_pack_bytes_degenerate_scale(rows, K, transpose, cls):
+    xc = _degenerate((K, rows) if transpose else (rows, K), cls, seed=3)
+    _check_degenerate_image(xc, _pack(xc.to(_dev()), transpose), transpose, cls)
+
+
+@pytest.mark.parametrize("cls", list(DEGENERATE))
+def test_p2_pack_ladder_and_zero_degenerate_scale(cls):
+    """test_p2_pack_ladder_and_zero at the ends of the scale's range: rows from 1 down to 2^-31.5 of the max, an all-zero row;
+    the tiny classes run into fp32-subnormal elements on the way down (only required to be finite).  The ladders of `zero`
+    (all zero) and `t126` (all subnormal) are degenerate, and run under the same mask."""
+    xc = _degenerate((64, 128), cls, seed=5)
+    for r in range(64):
+        xc[r] = torch.ldexp(xc[r], torch.tensor(-(r // 2))) * (1.0 if r % 2 == 0 else 0.70703125)
+    xc[7] = 0
+    img = _pack(xc.to(_dev()))
+    _check_degenerate_image(xc, img, False, cls)
+    assert not bool(_image_view(img.data)[7].cpu().view(torch.int16).any())          # the zero row: (+0, +0) everywhere
 
 
 @pytest.mark.parametrize("M,N,K", [(256, 128, 32), (256, 128, 64), (1000, 384, 96), (4096, 512, 512), (16384, 512, 512), (300, 132, 512)])
@@ -166,6 +203,23 @@ def test_layernorm_p2_image_and_gemm():
     G.gemm(y0, wt, ref, M, 384, d)
     G.gemm_p2(G.P2Image(yp, L.amax_of(y)), _pack(wt), out, M, 384, d)
     assert torch.equal(out, ref)
+
+
+def test_layernorm_p2_image_zero_weight_and_bias():
+    """w == 0 and b == 0: the a-priori bound max |w| sqrt(d - 1) + max |b| is 0, the image's scale is the clamped one -- the
+    image must be all zero bytes (not 0 * inf = NaN in the lo plane) and y exactly 0; a product fed by it is exactly 0."""
+    from lvt_amd.hip import gemm as G, ew, binding as L
+    M, d = 256, 512
+    x, w, b = _rand(M, d, scale=3.0), torch.zeros(d, device=_dev()), torch.zeros(d, device=_dev())
+    y, yp, _, _ = ew.layernorm_fwd_p2(x, w, b)
+    assert float(L.amax_of(y)) == 0.0
+    assert not bool(y.view(torch.int32).any())
+    assert not bool(_image_view(yp).view(torch.int16).any())
+    wt = _rand(128, d, seed=3)
+    out = torch.full((M, 128), float("nan"), device=_dev())
+    G.gemm_p2(G.P2Image(yp, L.amax_of(y)), _pack(wt), out, M, 128, d)
+    assert not bool(out.view(torch.int32).any())
+    assert float(L.amax_of(out)) == 0.0
 
 
 def test_gemm_p2_output_image():

@@ -34,7 +34,8 @@ VALUES = ("uniform", "heavy_tail", "zero_tile")
 def _operand(k, cols, values, seed):
     """(k, cols) fp32, cols contiguous.  heavy_tail: a few entries 2^20 times the rest (the scale comes from the max, the
     bulk lives in the low plane's range); zero_tile: the first 32 k of the first 128 columns, one staged tile, are zero
-    (half of them where that tile is the whole operand: a product with an operand whose max |.| is 0 is not a case here)."""
+    (half of them where that tile is the whole operand); zero_all: the whole operand is zero, its max |.| record is 0
+    (test_zero_operand_equals_nt only)."""
     g = torch.Generator().manual_seed(1000 * seed + 7 * k + cols)
     t = torch.rand(k, cols, generator=g) * 2 - 1
     if values == "heavy_tail":
@@ -43,6 +44,8 @@ def _operand(k, cols, values, seed):
         t.view(-1)[idx] *= 2.0 ** 20
     elif values == "zero_tile":
         t[:32, :128 if t.numel() > 32 * 128 else 64] = 0
+    elif values == "zero_all":
+        t.zero_()
     return t
 
 
@@ -138,3 +141,23 @@ def test_batched_equals_nt(ta):
     want = torch.full((2, M, N), float("nan"), device=d)
     G.gemm(xt, yt, want, M, N, K, ta=0, tb=0, batch_inner=2, sA=(0, M * K), sB=(0, K * N), sC=(0, M * N))
     assert torch.equal(got, want)
+
+
+@pytest.mark.parametrize("zero", ["x", "y"])
+@pytest.mark.parametrize("M,N,K,splits", [(256, 128, 32, 1), (260, 132, 96, 3)])
+def test_zero_operand_equals_nt(M, N, K, splits, zero):
+    """values = zero_all: a WHOLE operand is zero (max |.| record 0: the scale's exponent sits at its clamp, and s * 2048 of the
+    split must stay finite).  TN and NN equal NT bit for bit, and the product is +0 everywhere -- not 0 * inf = NaN."""
+    from lvt_amd.hip import gemm as G
+    d = _dev()
+    x = _operand(K, M, "zero_all" if zero == "x" else "uniform", 1).to(d)
+    y = _operand(K, N, "zero_all" if zero == "y" else "uniform", 2).to(d)
+    xt, yt = _transposed_like(x, x), _transposed_like(y, y)
+    want = torch.full((M, N), float("nan"), device=d)
+    G.gemm(xt, yt, want, M, N, K, ta=0, tb=0, splits=splits)
+    tn = torch.full((M, N), float("nan"), device=d)
+    G.gemm(x, y, tn, M, N, K, ta=1, tb=1, splits=splits)
+    nn = torch.full((M, N), float("nan"), device=d)
+    G.gemm(xt, y, nn, M, N, K, ta=0, tb=1, splits=splits)
+    assert not bool(want.view(torch.int32).any())
+    assert torch.equal(tn.view(torch.int32), want.view(torch.int32)) and torch.equal(nn.view(torch.int32), want.view(torch.int32))
