@@ -410,8 +410,9 @@ int lvt_layernorm_fwd(const float *x, long long rows, int d, float eps, const fl
                       float *y, float *mean, float *rstd, float *y_amax, const float *w_amax, const float *b_amax,
                       void *stream);
 /* (y_amax / dx_amax, nullable: max |y| resp. max |dx| folded into a device scalar as lvt_amax_io.c is.  With w_amax and
- *  b_amax -- device scalars >= max |w|, max |b| -- the forward STORES the bound max |w| sqrt(d - 1) + max |b| into *y_amax
- *  instead of reducing: |(x - mean) rstd| <= sqrt(d - 1) on every row.)                                                   */
+ *  b_amax -- device scalars >= max |w|, max |b| -- the forward STORES the bound (max |w| sqrt(d - 1) + max |b|) (1 + 2^-20) into
+ *  *y_amax instead of reducing: |(x - mean) rstd| <= sqrt(d - 1) on every row in exact arithmetic, and the relative 2^-20 covers
+ *  the fp32 rounding of the kernel's own mean, rstd and products (a one-hot row comes out up to 2 ulp above sqrtf(d - 1)).)  */
 /* The same forward that ALSO writes y as a P2 image `yp` (ABI 600; row pitch d floats, d % 32 == 0) under the scale of the
  * a-priori bound it stores into *y_amax: w_amax, b_amax and y_amax are required.  The image feeds lvt_gemm_p2_f32 (a_planes). */
 int lvt_layernorm_fwd_p2(const float *x, long long rows, int d, float eps, const float *w, const float *b,

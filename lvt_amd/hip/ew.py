@@ -91,7 +91,8 @@ def layernorm_fwd(x, w, b, eps=1e-5, save_stats=True):
     y = torch.empty_like(x)
     mean = _f32(rows, like=x) if save_stats else None
     rstd = _f32(rows, like=x) if save_stats else None
-    # f16x2: the output feeds engine launches; its max |.| is the a-priori bound max |w| sqrt(d - 1) + max |b| (one store)
+    # f16x2: the output feeds engine launches; its max |.| is the a-priori bound (max |w| sqrt(d - 1) + max |b|) (1 + 2^-20) (one
+    # store; the 2^-20 covers the kernel's own fp32 rounding: tests/test_gpu_row_kernels.py)
     f16 = L.f16x2()
     L.check(L.lib().lvt_layernorm_fwd(L.ptr(x), rows, d, eps, L.ptr(w), L.ptr(b), L.ptr(y), L.ptr(mean),
                                       L.ptr(rstd), L.out_amax(y), L.ptr(L.amax_of(w)) if f16 else None,

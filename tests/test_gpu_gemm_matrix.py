@@ -21,11 +21,10 @@ import pytest
 import torch
 
 from lvt_amd.hip import binding as L, gemm as G
+from util_guard import PAD, PAYLOAD, Buf
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-PAD = 64                                   # floats of payload before and after every buffer
-PAYLOAD = 0x7FC0DEAD                       # a quiet NaN with a recognisable mantissa
 EPS_ACC, EPS_EPI = 1e-5, 2.0 ** -21
 B_, R_, U_, M_ = L.EPI_BIAS, L.EPI_RESIDUAL, L.EPI_RELU, L.EPI_MASK
 T_, A_ = L.EPI_TANH, L.EPI_ACCUM
@@ -46,33 +45,6 @@ def mode(request):
 # ---- buffers ---------------------------------------------------------------------------------------------------------
 def _r4(x):
     return (x + 3) // 4 * 4
-
-
-class Buf:
-    """A NaN-payload buffer (PAD floats before and after) holding `values` at element offsets `idx` (same shape)."""
-
-    def __init__(self, idx, values=None, dtype=torch.float32, start=PAD):
-        self.idx, self.start = idx, start
-        n = (int(idx.max()) + 1) if idx.numel() else 0
-        host = torch.full((start + n + PAD,), PAYLOAD, dtype=torch.int32).view(torch.float32)
-        if values is not None:
-            host[start + idx.reshape(-1)] = values.reshape(-1).float()
-        self.dev = host.to(DEV)
-        self.view = self.dev[start:]
-        if dtype != torch.float32:
-            self.view = self.view.view(dtype)
-
-    def logical(self):
-        return self.dev.cpu()[self.start + self.idx]
-
-    def outside_untouched(self):
-        bits = self.dev.cpu().view(torch.int32)
-        keep = torch.ones(bits.numel(), dtype=torch.bool)
-        keep[self.start + self.idx.reshape(-1)] = False
-        return bool((bits[keep] == PAYLOAD).all())
-
-    def bits(self):
-        return self.dev.cpu().view(torch.int32)
 
 
 def _zoff(bo, bi, s_o, s_i):
