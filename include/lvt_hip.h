@@ -33,7 +33,7 @@ extern "C" {
 #define LVT_ENODEVICE   (-4)   /* no gfx950 device visible                             */
 
 const char *lvt_last_error(void);
-int lvt_version(void);          /* 650 = sigmoid output activation (ABI changes are listed in INTEGRATION.md) */
+int lvt_version(void);          /* 660 = leaky activation / mask, 2x2 pool and upsample (ABI changes are listed in INTEGRATION.md) */
 /* Device probe: name, CU count, clock (kHz), HBM bytes.  Returns LVT_ENODEVICE without a GPU. */
 int lvt_device_info(char *name, int name_len, int *cus, int *clock_khz, long long *hbm_bytes);
 
@@ -92,7 +92,7 @@ int lvt_amax_merge(const float *a, const float *b, float *out, void *stream);
 #define LVT_EPI_RESIDUAL    2   /* + res[m][n]                                                 */
 #define LVT_EPI_RELU        4   /* max(.,0)                                                    */
 #define LVT_EPI_TANH        8   /* tanhf(.)                                                    */
-#define LVT_EPI_MASK       16   /* * (mask[m][n] > 0)   (ReLU backward with the saved output)  */
+#define LVT_EPI_MASK       16   /* * (mask[m][n] > 0)   (ReLU backward with the saved output; see LVT_EPI_LEAKY_MASK) */
 #define LVT_EPI_ACCUM      32   /* C += result                                                 */
 #define LVT_EPI_PLANES     64   /* lvt_gemm_f32 only: C is a bf16 image and receives the result as its EXACT 3-way bf16 split
                                  * (v = p1 + p2 + p3, round-to-nearest-even at every level): plane j of element (m, n) at
@@ -106,6 +106,16 @@ int lvt_amax_merge(const float *a, const float *b, float *out, void *stream);
  * themselves).  Ignored without LVT_EPI_SIGMOID.                                                                            */
 #define LVT_EPI_PAD(n)    (((n) & 3) << 24)
 #define LVT_EPI_PAD_OF(flags) (((flags) >> 24) & 3)
+/* LeakyReLU with the FIXED slope 0.2 -- the only one the reference uses (vidgen/modeling/encoder/convencoder.py,
+ * generator/convdecoder.py: nn.LeakyReLU(0.2)) -- ABI 660: x > 0 ? x : 0.2f * x, in the place of RELU (after bias and residual).
+ * Accepted wherever LVT_EPI_RELU is: lvt_conv3d_fwd / _fwd_parity, lvt_conv3d_bwd_data / _bwd_data_phases, lvt_gemm_f32,
+ * lvt_bn_apply.  leaky(0) = 0, so pad channels stay 0.  Combined with RELU, TANH or SIGMOID: LVT_EINVAL.                      */
+#define LVT_EPI_LEAKY       (1 << 11)
+/* Qualifies LVT_EPI_MASK (ABI 660; LVT_EINVAL without it): the result is multiplied by (mask > 0 ? 1 : 0.2f) instead of
+ * (mask > 0) -- LeakyReLU backward with the saved POST-activation output as the mask (the slope is positive, so its sign is the
+ * pre-activation's; an exact 0 takes the 0.2 branch, as torch's leaky_relu_backward).  A flag of its own, not MASK | LEAKY: a
+ * launch may apply an activation and a mask of different kinds.  Accepted wherever LVT_EPI_MASK is (lvt_gemm_p2_f32 excepted). */
+#define LVT_EPI_LEAKY_MASK  (1 << 12)
 /* causal structure of the batched attention products of a masked layer (M, N, K token positions of one block):          */
 #define LVT_CAUSAL_KMAX   (1 << 8)    /* A(m,k) == 0 for k > m: a tile reduces over k < m0 + 128 only  (dQ = dS K)        */
 #define LVT_CAUSAL_KMIN   (1 << 9)    /* A(m,k) == 0 for k < m: a tile starts its reduction at k = m0  (dV = P^T dO, dK)  */
@@ -616,7 +626,8 @@ int lvt_bn_stats(const float *y, long long M, int Cp, float *stats, void *worksp
 int lvt_bn_finalize(const float *stats, int nranks, long long count, int C, int Cp, const float *gamma, const float *beta,
                     float *running_mean, float *running_var, long long *num_batches_tracked, float momentum, float eps,
                     int flags, float *scale, float *shift, float *saved, void *stream);
-/* out = act(y * scale[c] + shift[c] (+ res)), act = LVT_EPI_RELU / LVT_EPI_TANH / LVT_EPI_SIGMOID / none (flags); res nullable.
+/* out = act(y * scale[c] + shift[c] (+ res)), act = LVT_EPI_RELU / LVT_EPI_LEAKY / LVT_EPI_TANH / LVT_EPI_SIGMOID / none (flags);
+ * res nullable.
  * With LVT_EPI_SIGMOID | LVT_EPI_PAD(n) the last n channels of every row are stored as 0 (ABI 650).
  * out_amax (nullable): max |out| folded in as by the engine's c_amax.                                                    */
 int lvt_bn_apply(const float *y, const float *res, long long M, int Cp, const float *scale, const float *shift, int flags,
@@ -640,6 +651,26 @@ typedef struct {
     float *bias_out; float *w_amax;
 } lvt_bn_fold_entry;
 int lvt_bn_fold(const lvt_bn_fold_entry *entries, int n, void *stream);
+
+
+/* ---- 2x2 average pool and nearest 2x upsample, channels-last (ABI 660; csrc/resample.hip).  nn.AvgPool2d(2) and
+ * nn.Upsample(scale_factor=2) of vidgen/modeling/encoder/convencoder.py:47 / generator/convdecoder.py:40, and each other's
+ * backward.  x, out, mask: fp32 (N, H, W, Cp) resp. the output's shape, Cp % 4 == 0, 16-byte aligned; 16-byte accesses along
+ * the channels, every input and output element touched once.
+ *   lvt_pool2x2    : out[n,i,j,c] = scale * (x[n,2i,2j,c] + x[n,2i,2j+1,c] + x[n,2i+1,2j,c] + x[n,2i+1,2j+1,c]), out (N,H/2,W/2,Cp).
+ *                    scale 0.25: AvgPool2d(2); scale 1: the backward of the upsample.  H and W must be EVEN (LVT_EINVAL
+ *                    otherwise): the reference floors an odd extent, but none of its image sizes is odd.
+ *   lvt_upsample2x2: out[n,2i+a,2j+b,c] = scale * x[n,i,j,c], a, b in {0, 1}, out (N,2H,2W,Cp).  scale 1: Upsample(2), a
+ *                    bit-exact copy; scale 0.25: the backward of the average pool.
+ * mask (nullable), mask_flags = LVT_EPI_MASK or LVT_EPI_MASK | LVT_EPI_LEAKY_MASK: the output is multiplied by (mask > 0) resp.
+ * (mask > 0 ? 1 : 0.2f), mask the saved post-activation output of the layer in front -- in the backward roles the activation
+ * backward of that layer rides on this launch, as on the engine's epilogues.  mask_flags must be 0 without a mask.
+ * out_amax (nullable): max |out| folded in as by the engine's c_amax (integer max on the bit pattern: order-independent).  No
+ * floating-point atomics, fixed summation order: two runs give the same bits.                                              */
+int lvt_pool2x2(const float *x, int N, int H, int W, int Cp, float scale, const float *mask, int mask_flags, float *out,
+                float *out_amax, void *stream);
+int lvt_upsample2x2(const float *x, int N, int H, int W, int Cp, float scale, const float *mask, int mask_flags, float *out,
+                    float *out_amax, void *stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,7 @@
 // products of a transformer layer are one such tile per CU and launch: a third of their time.
 //
 // Here, for the plain forms (row-major C or the pixel permutation of the frame-resident convolutions, flags in {BIAS, RESIDUAL,
-// RELU, MASK}, or the split-K partial store):
+// RELU, MASK, LEAKY, LEAKY_MASK}, or the split-K partial store):
 //   * the flag set is a template parameter (the kernels switch over the six combinations the models use; anything else takes
 //     the run-time form of the same body);
 //   * a lane's column is fixed (bias loaded once), its rows step by 4;
@@ -69,6 +69,7 @@ __device__ __forceinline__ float lvt_epi_fast_wave(const LvtEpi &e, lvt_f32x16 (
     constexpr int SW = TN * 32;
     const int flags = F >= 0 ? F : e.flags;
     const bool f_bias = flags & LVT_EPI_BIAS, f_res = flags & LVT_EPI_RESIDUAL, f_relu = flags & LVT_EPI_RELU, f_mask = flags & LVT_EPI_MASK;
+    const bool f_leaky = flags & LVT_EPI_LEAKY, f_lkm = flags & LVT_EPI_LEAKY_MASK;      // (clear in every compile-time set but the two below)
     const int l31 = lane & 31, half = lane >> 5;
     const int c4 = lane & 15, r0 = lane >> 4;
     const int col = n_w + 4 * c4;
@@ -122,7 +123,8 @@ __device__ __forceinline__ float lvt_epi_fast_wave(const LvtEpi &e, lvt_f32x16 (
             if (f_bias) { v.x += bias4.x; v.y += bias4.y; v.z += bias4.z; v.w += bias4.w; }
             if (f_res) { v.x += rv[u].x; v.y += rv[u].y; v.z += rv[u].z; v.w += rv[u].w; }
             if (f_relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-            if (f_mask) { v.x = mv[u].x > 0.f ? v.x : 0.f; v.y = mv[u].y > 0.f ? v.y : 0.f; v.z = mv[u].z > 0.f ? v.z : 0.f; v.w = mv[u].w > 0.f ? v.w : 0.f; }
+            if (f_leaky) { v.x = lvt_leakyf(v.x); v.y = lvt_leakyf(v.y); v.z = lvt_leakyf(v.z); v.w = lvt_leakyf(v.w); }
+            if (f_mask) { v.x = lvt_maskf(v.x, mv[u].x, f_lkm); v.y = lvt_maskf(v.y, mv[u].y, f_lkm); v.z = lvt_maskf(v.z, mv[u].z, f_lkm); v.w = lvt_maskf(v.w, mv[u].w, f_lkm); }
             if (colok && row0 + 4 * u < e.M) {
                 am = fmaxf(am, fmaxf(fmaxf(lvt_absf(v.x), lvt_absf(v.y)), fmaxf(lvt_absf(v.z), lvt_absf(v.w))));
                 *reinterpret_cast<float4 *>(cp + orow[u] * e.ldc) = v;
@@ -137,7 +139,7 @@ template <int TM, int TN, class RM = LvtRowIdentity>
 __device__ __forceinline__ float lvt_epi_fast_dispatch(const LvtEpi &e, lvt_f32x16 (&acc)[TM][TN], float *wave_tile, int m_w, int n_w, int lane,
                                                        const RM rm = RM()) {
 #define LVT_EPI_CASE(F) case (F): return lvt_epi_fast_wave<(F), TM, TN, RM>(e, acc, wave_tile, m_w, n_w, lane, rm)
-    switch (e.flags & (LVT_EPI_BIAS | LVT_EPI_RESIDUAL | LVT_EPI_RELU | LVT_EPI_MASK)) {
+    switch (e.flags & (LVT_EPI_BIAS | LVT_EPI_RESIDUAL | LVT_EPI_RELU | LVT_EPI_MASK | LVT_EPI_LEAKY | LVT_EPI_LEAKY_MASK)) {
     LVT_EPI_CASE(0);
     LVT_EPI_CASE(LVT_EPI_BIAS);
     LVT_EPI_CASE(LVT_EPI_BIAS | LVT_EPI_RELU);
@@ -146,6 +148,8 @@ __device__ __forceinline__ float lvt_epi_fast_dispatch(const LvtEpi &e, lvt_f32x
     LVT_EPI_CASE(LVT_EPI_RESIDUAL);
     LVT_EPI_CASE(LVT_EPI_MASK);
     LVT_EPI_CASE(LVT_EPI_RESIDUAL | LVT_EPI_MASK);
+    LVT_EPI_CASE(LVT_EPI_BIAS | LVT_EPI_LEAKY);                    // the conv + LeakyReLU layers of ConvEncoder / ConvDecoder
+    LVT_EPI_CASE(LVT_EPI_MASK | LVT_EPI_LEAKY_MASK);               // and their data gradients
     default: return lvt_epi_fast_wave<-1, TM, TN, RM>(e, acc, wave_tile, m_w, n_w, lane, rm);
     }
 #undef LVT_EPI_CASE

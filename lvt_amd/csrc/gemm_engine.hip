@@ -760,9 +760,10 @@ __device__ __forceinline__ void lvt_epilogue(const KParams &p, f32x16 (&acc)[BM 
                 if (flags & LVT_EPI_BIAS) v += p.bias[col];
                 if (flags & LVT_EPI_RESIDUAL) v += p.res[coff + orow * p.ldr + col];
                 if (flags & LVT_EPI_RELU) v = fmaxf(v, 0.f);
+                if (flags & LVT_EPI_LEAKY) v = lvt_leakyf(v);
                 if (flags & LVT_EPI_TANH) v = tanhf(v);
                 if (flags & LVT_EPI_SIGMOID) v = lvt_sigmoid_col(v, col < p.N - LVT_EPI_PAD_OF(flags));
-                if (flags & LVT_EPI_MASK) v = (p.mask[coff + orow * p.ldm + col] > 0.f) ? v : 0.f;
+                if (flags & LVT_EPI_MASK) v = lvt_maskf(v, p.mask[coff + orow * p.ldm + col], flags & LVT_EPI_LEAKY_MASK);
                 float *cp = p.C + coff + orow * p.ldc + col;
                 if (flags & LVT_EPI_ACCUM) v += *cp;
                 *cp = v;
@@ -852,6 +853,7 @@ __device__ __forceinline__ void lvt_epilogue_vec(const KParams &p, f32x16 (&acc)
         rw = ((fw - g.pw) % g.sw + g.sw) % g.sw;
     }
     const int flags = p.flags;
+    const bool lkm = flags & LVT_EPI_LEAKY_MASK;
     float am = 0.f;
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
@@ -860,7 +862,10 @@ __device__ __forceinline__ void lvt_epilogue_vec(const KParams &p, f32x16 (&acc)
 #pragma unroll
             for (int r = 0; r < 16; ++r) tile[((r & 3) + 8 * (r >> 2) + 4 * half) * SW + 32 * j + l31] = acc[i][j][r];
         __syncthreads();
-        if (AMODE != A_KPLAIN && AMODE != A_MPLAIN && p.splits <= 1 && (flags & LVT_EPI_MASK) && !(flags & (LVT_EPI_PLANES | LVT_EPI_ACCUM))) {
+        // (launches with a leaky activation or mask take the general loop below: the two-phase form is at its register limit --
+        //  two more live values per element cost the 128 x 128 transposed-convolution kernel its second wave per SIMD)
+        if (AMODE != A_KPLAIN && AMODE != A_MPLAIN && p.splits <= 1 && (flags & LVT_EPI_MASK) &&
+            !(flags & (LVT_EPI_PLANES | LVT_EPI_ACCUM | LVT_EPI_LEAKY | LVT_EPI_LEAKY_MASK))) {
             constexpr int NU = 32 * C4 / 64;
             // MASK forms of the convolution kernels (ReLU-backward: the mask is an activation of the forward pass, cold in the
             // caches): every mask / residual value of the sub-tile is requested before the first store -- a load may not pass an
@@ -952,6 +957,7 @@ __device__ __forceinline__ void lvt_epilogue_vec(const KParams &p, f32x16 (&acc)
                         if (flags & LVT_EPI_BIAS) { const float4 b = ldg4(p.bias + col); v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w; }
                         if (flags & LVT_EPI_RESIDUAL) { const float4 b = ldg4(p.res + coff + orow * p.ldr + col); v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w; }
                         if (flags & LVT_EPI_RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+                        if (flags & LVT_EPI_LEAKY) { v.x = lvt_leakyf(v.x); v.y = lvt_leakyf(v.y); v.z = lvt_leakyf(v.z); v.w = lvt_leakyf(v.w); }
                         if (flags & LVT_EPI_TANH) { v.x = tanhf(v.x); v.y = tanhf(v.y); v.z = tanhf(v.z); v.w = tanhf(v.w); }
                         if (flags & LVT_EPI_SIGMOID) {          // (N is a multiple of 4: the pads are the tail of the last float4)
                             const int nr = p.N - LVT_EPI_PAD_OF(flags) - col;
@@ -959,7 +965,7 @@ __device__ __forceinline__ void lvt_epilogue_vec(const KParams &p, f32x16 (&acc)
                         }
                         if (flags & LVT_EPI_MASK) {
                             const float4 mk = ldg4(p.mask + coff + orow * p.ldm + col);
-                            v.x = mk.x > 0.f ? v.x : 0.f; v.y = mk.y > 0.f ? v.y : 0.f; v.z = mk.z > 0.f ? v.z : 0.f; v.w = mk.w > 0.f ? v.w : 0.f;
+                            v.x = lvt_maskf(v.x, mk.x, lkm); v.y = lvt_maskf(v.y, mk.y, lkm); v.z = lvt_maskf(v.z, mk.z, lkm); v.w = lvt_maskf(v.w, mk.w, lkm);
                         }
                         if (!(flags & LVT_EPI_ACCUM)) am = fmaxf(am, fmaxf(fmaxf(lvt_absf(v.x), lvt_absf(v.y)), fmaxf(lvt_absf(v.z), lvt_absf(v.w))));
                         if (flags & LVT_EPI_PLANES) {
@@ -2086,6 +2092,7 @@ extern "C" int lvt_gemm_f32(const lvt_gemm_desc *d, void *workspace, size_t work
     LVT_REQUIRE(!(d->flags & LVT_EPI_BIAS) || d->bias, "gemm: BIAS flag without bias");
     LVT_REQUIRE(!(d->flags & LVT_EPI_RESIDUAL) || d->res, "gemm: RESIDUAL flag without res");
     LVT_REQUIRE(!(d->flags & LVT_EPI_MASK) || d->mask, "gemm: MASK flag without mask");
+    LVT_REQUIRE_EPI(d->flags, "gemm");
     LVT_REQUIRE(math_of(d->flags) != 2 || (d->a_amax && d->b_amax), "gemm: LVT_MATH_F16X2 needs a_amax and b_amax");
     LVT_REQUIRE(!d->c_amax || d->splits <= 1, "gemm: c_amax is not produced by split-K launches");
     if (d->flags & LVT_EPI_PLANES)
@@ -2318,6 +2325,7 @@ extern "C" int lvt_conv3d_fwd_parity(const lvt_conv_geom *g, const float *x, con
     LVT_REQUIRE(!(flags & LVT_EPI_RESIDUAL) || res, "conv3d_fwd_parity: RESIDUAL without res");
     LVT_REQUIRE(!(flags & LVT_EPI_MASK) || mask, "conv3d_fwd_parity: MASK without mask");
     LVT_REQUIRE(!(flags & LVT_EPI_ACCUM), "conv3d_fwd_parity: unsupported flag");
+    LVT_REQUIRE_EPI(flags, "conv3d_fwd_parity");
     LVT_REQUIRE(lvt_aligned16(x) && lvt_aligned16(wq) && lvt_aligned16(y) && lvt_aligned16(bias) && lvt_aligned16(res) &&
                 lvt_aligned16(mask), "conv3d_fwd_parity: alignment");
     KParams p; memset(&p, 0, sizeof(p));
@@ -2355,6 +2363,7 @@ extern "C" int lvt_conv3d_fwd(const lvt_conv_geom *g, const float *x, const floa
     LVT_REQUIRE(!(flags & LVT_EPI_RESIDUAL) || res, "conv3d_fwd: RESIDUAL without res");
     LVT_REQUIRE(!(flags & LVT_EPI_MASK) || mask, "conv3d_fwd: MASK without mask");
     LVT_REQUIRE(!(flags & LVT_EPI_ACCUM), "conv3d_fwd: unsupported flag");
+    LVT_REQUIRE_EPI(flags, "conv3d_fwd");
     const long long M = (long long)g->N * g->To * g->Ho * g->Wo;
     LVT_REQUIRE(M < 0x7fffffffLL, "conv3d_fwd: too many output positions");
     KParams p; memset(&p, 0, sizeof(p));
@@ -2434,6 +2443,7 @@ extern "C" int lvt_conv3d_bwd_data_phases(const lvt_conv_geom *g, const float *d
     LVT_REQUIRE(!(flags & LVT_EPI_RESIDUAL) || res, "conv3d_bwd_data_phases: RESIDUAL without res");
     LVT_REQUIRE(!(flags & LVT_EPI_MASK) || mask, "conv3d_bwd_data_phases: MASK without mask");
     LVT_REQUIRE(!(flags & LVT_EPI_ACCUM), "conv3d_bwd_data_phases: unsupported flag");
+    LVT_REQUIRE_EPI(flags, "conv3d_bwd_data_phases");
     LVT_REQUIRE(lvt_aligned16(dy) && lvt_aligned16(wph) && lvt_aligned16(dx) && lvt_aligned16(bias) && lvt_aligned16(res) &&
                 lvt_aligned16(mask), "conv3d_bwd_data_phases: alignment");
     KParams p; memset(&p, 0, sizeof(p));
@@ -2470,6 +2480,7 @@ extern "C" int lvt_conv3d_bwd_data(const lvt_conv_geom *g, const float *dy, cons
     LVT_REQUIRE(!(flags & LVT_EPI_RESIDUAL) || res, "conv3d_bwd_data: RESIDUAL without res");
     LVT_REQUIRE(!(flags & LVT_EPI_MASK) || mask, "conv3d_bwd_data: MASK without mask");
     LVT_REQUIRE(!(flags & LVT_EPI_ACCUM), "conv3d_bwd_data: unsupported flag");
+    LVT_REQUIRE_EPI(flags, "conv3d_bwd_data");
     KParams p; memset(&p, 0, sizeof(p));
     p.Tq = g->Ti / g->st; p.Hq = g->Hi / g->sh; p.Wq = g->Wi / g->sw;
     p.jT = g->Kt / g->st; p.jH = g->Kh / g->sh; p.jW = g->Kw / g->sw;

@@ -25,6 +25,13 @@ void lvt_set_error(const char *fmt, ...);
     } while (0)
 
 static inline bool lvt_aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
+// the activation / mask flags of an epilogue go together: LEAKY excludes the other activations, LEAKY_MASK qualifies MASK
+static inline bool lvt_epi_flags_ok(int flags) {
+    if ((flags & LVT_EPI_LEAKY) && (flags & (LVT_EPI_RELU | LVT_EPI_TANH | LVT_EPI_SIGMOID))) return false;
+    return !(flags & LVT_EPI_LEAKY_MASK) || (flags & LVT_EPI_MASK);
+}
+#define LVT_REQUIRE_EPI(flags, name)                                                                                         \
+    LVT_REQUIRE(lvt_epi_flags_ok(flags), "%s: LVT_EPI_LEAKY excludes RELU / TANH / SIGMOID, and LVT_EPI_LEAKY_MASK needs LVT_EPI_MASK", name)
 static inline __host__ __device__ long long lvt_cdiv(long long a, long long b) { return (a + b - 1) / b; }
 
 // 256 CUs x 8 XCDs on MI355X; used only to size grids / split-K, never for correctness.
@@ -54,6 +61,12 @@ __device__ __forceinline__ float lvt_sigmoidf(float v) {
     return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(v * -1.44269504088896341f));
 }
 __device__ __forceinline__ float lvt_sigmoid_col(float v, bool real) { return real ? lvt_sigmoidf(v) : 0.f; }
+// LVT_EPI_LEAKY: v > 0 ? v : 0.2 v as one multiply and one max (0.2 v > v exactly when v < 0; leaky(0) = 0, NaN stays NaN).
+#define LVT_LEAKY_SLOPE 0.2f
+__device__ __forceinline__ float lvt_leakyf(float v) { return fmaxf(v, LVT_LEAKY_SLOPE * v); }
+// LVT_EPI_MASK (+ LVT_EPI_LEAKY_MASK): v where the saved output m is positive, else 0 (ReLU) or 0.2 v (leaky; an exact 0 of m takes
+// the 0.2 branch, torch's leaky_relu_backward rule)
+__device__ __forceinline__ float lvt_maskf(float v, float m, bool leaky) { return m > 0.f ? v : (leaky ? LVT_LEAKY_SLOPE * v : 0.f); }
 __device__ __forceinline__ void lvt_block_amax_commit(float m, float *dst, float *scratch) {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));

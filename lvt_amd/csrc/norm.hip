@@ -225,6 +225,7 @@ __global__ void lvt_bn_finalize_kernel(const float *__restrict__ stats, int nran
 // real: the channel is not one of the zero pads (only the sigmoid, whose value at 0 is not 0, needs to know)
 __device__ __forceinline__ float bn_act(float v, int flags, bool real) {
     if (flags & LVT_EPI_RELU) return fmaxf(v, 0.f);
+    if (flags & LVT_EPI_LEAKY) return lvt_leakyf(v);
     if (flags & LVT_EPI_TANH) return tanhf(v);
     if (flags & LVT_EPI_SIGMOID) return lvt_sigmoid_col(v, real);
     return v;
@@ -433,6 +434,8 @@ extern "C" int lvt_bn_finalize(const float *stats, int nranks, long long count, 
 extern "C" int lvt_bn_apply(const float *y, const float *res, long long M, int Cp, const float *scale, const float *shift,
                             int flags, float *out, float *out_amax, void *stream) {
     LVT_REQUIRE(y && scale && shift && out && M > 0 && Cp > 0 && Cp % 4 == 0, "lvt_bn_apply: bad arguments");
+    LVT_REQUIRE(!(flags & LVT_EPI_LEAKY) || !(flags & (LVT_EPI_RELU | LVT_EPI_TANH | LVT_EPI_SIGMOID)),
+                "lvt_bn_apply: LVT_EPI_LEAKY excludes RELU / TANH / SIGMOID");
     LVT_REQUIRE(lvt_aligned16(y) && lvt_aligned16(out) && lvt_aligned16(scale) && lvt_aligned16(shift) && (!res || lvt_aligned16(res)),
                 "lvt_bn_apply: operands must be 16-byte aligned");
     const long long n4 = M * Cp / 4;

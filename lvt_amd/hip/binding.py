@@ -14,6 +14,7 @@ _LIB_PATH = os.environ.get("LVT_HIP_LIB") or os.path.join(os.path.dirname(_HERE)
 
 EPI_BIAS, EPI_RESIDUAL, EPI_RELU, EPI_TANH, EPI_MASK, EPI_ACCUM, EPI_PLANES = 1, 2, 4, 8, 16, 32, 64
 EPI_SIGMOID = 128
+EPI_LEAKY, EPI_LEAKY_MASK = 1 << 11, 1 << 12   # LeakyReLU(0.2) activation; with EPI_MASK: its backward rule (include/lvt_hip.h)
 
 
 def epi_pad(n):
@@ -22,7 +23,7 @@ def epi_pad(n):
         raise ValueError("epi_pad: 0..3 pad channels, got %r" % (n,))
     return n << 24
 CAUSAL_KMAX, CAUSAL_KMIN, CAUSAL_TILE = 1 << 8, 1 << 9, 1 << 10      # causal attention products (include/lvt_hip.h)
-ABI_VERSION = 650           # lvt_version() of the library this module binds (argument lists below)
+ABI_VERSION = 660           # lvt_version() of the library this module binds (argument lists below)
 MATH_F32 = 1 << 16          # per-call arithmetic selectors of the engine entry points (include/lvt_hip.h)
 MATH_F16X2 = 1 << 18
 ONEHOT_DENSE = 1 << 19
@@ -217,6 +218,8 @@ def _declare(lib):
         "lvt_bn_bwd_reduce": (ci, [vp, vp, cll, ci, vp, vp, vp, sz, vp]),
         "lvt_bn_bwd_apply": (ci, [vp, vp, cll, ci, vp, vp, vp, cll, ci, vp, vp, vp]),
         "lvt_bn_fold": (ci, [P(BnFoldEntry), ci, vp]),
+        "lvt_pool2x2": (ci, [vp, ci, ci, ci, ci, cf, vp, ci, vp, vp, vp]),
+        "lvt_upsample2x2": (ci, [vp, ci, ci, ci, ci, cf, vp, ci, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)

@@ -1,5 +1,6 @@
-"""Fused conv-stack executor: runs a chain of (transposed) convolutions with bias / ReLU / tanh / sigmoid /
-residual epilogues on the implicit-GEMM engine, and its hand-scheduled backward.
+"""Fused conv-stack executor: runs a chain of (transposed) convolutions with bias / ReLU / LeakyReLU / tanh / sigmoid /
+residual epilogues on the implicit-GEMM engine, 2x2 average pools and nearest upsamples between them, and its hand-scheduled
+backward.
 
 Every activation is stored once, post-activation and channels-last.  ReLU backward is folded into
 the epilogue of the kernel that produces the upstream gradient (mask = saved post-ReLU output) and
@@ -18,6 +19,11 @@ and keeps that pre-norm output; the statistics, finalize and apply kernels then 
 residual in the apply).  Its backward runs the BN backward (reduce + apply) between the incoming gradient and the conv's
 weight and data gradients; the residual branch still receives the gradient at the add.  A no-grad forward whose norms
 all use running statistics folds them into the conv weight and bias instead and runs the plain stack.
+
+Resampling (Layer.kind "pool" / "up", csrc/resample.hip): parameter-less layers whose list entries in `params`, the weight packs
+and the gradients are (None, None) / None, so layer indices (res_from, norms) count them.  Each is the other's backward -- pool
+with scale 1 under an upsample, upsample with scale 0.25 under a pool -- and that launch applies the (Leaky)ReLU mask of the layer
+in front, like the data-gradient epilogues of the convolutions.
 """
 
 import torch
@@ -30,9 +36,10 @@ from . import norm as BN
 class Layer:
     """One conv / ConvTranspose layer of a stack.
 
-    kind: "conv" | "convT".  For convT the geometry is that of the equivalent forward conv whose
+    kind: "conv" | "convT" | "pool" | "up" (the last two: AvgPool2d(2) / Upsample(scale_factor=2); no parameters, no activation,
+    no norm, cin == cout; see Layer.resample).  For convT the geometry is that of the equivalent forward conv whose
     backward-data IS this layer (Ci = out channels of the ConvTranspose, Co = its in channels).
-    act: "" | "relu" | "tanh" | "sigmoid" (the last two on the last layer of a stack only).  res_from: index of an earlier
+    act: "" | "relu" | "leaky" (LeakyReLU(0.2)) | "tanh" | "sigmoid" (the last two on the last layer of a stack only).  res_from: index of an earlier
     output added before the activation (-1: none).  ci_real / co_real: channel counts of the torch-layout weight (pads excluded).
     norm: "" | "bn" | "syncbn" | "frozen": batch normalisation between the conv and the residual add / activation; the
     module that holds its tensors is handed to stack_forward per call (`norms`).
@@ -42,10 +49,16 @@ class Layer:
         self.kind, self.kernel, self.stride, self.pad = kind, kernel, stride, pad
         self.cin, self.cout, self.act, self.res_from = cin, cout, act, res_from
         self.norm = norm
+        self.resamples = kind in ("pool", "up")
 
     @staticmethod
     def pad4(c):
         return (c + 3) // 4 * 4
+
+    @classmethod
+    def resample(cls, kind, channels):
+        assert kind in ("pool", "up")
+        return cls(kind, None, None, None, channels, channels)
 
 
 def _geom(layer, x_shape):
@@ -73,7 +86,7 @@ def _act_flag(ly):
     kernels then store as 0 like every other epilogue does by itself."""
     if ly.act == "sigmoid":
         return L.EPI_SIGMOID | L.epi_pad(Layer.pad4(ly.cout) - ly.cout)
-    return {"": 0, "relu": L.EPI_RELU, "tanh": L.EPI_TANH}[ly.act]
+    return {"": 0, "relu": L.EPI_RELU, "leaky": L.EPI_LEAKY, "tanh": L.EPI_TANH}[ly.act]
 
 
 def _world():
@@ -143,6 +156,12 @@ def stack_forward(layers, x, params, want_grad=True, norms=None):
     pb = G.PackBatch()
     shape = tuple(x.shape)
     for i, (ly, (w, b)) in enumerate(zip(layers, params)):
+        if ly.resamples:
+            N, T, H, W, Cp = shape
+            shape = (N, T, H // 2, W // 2, Cp) if ly.kind == "pool" else (N, T, 2 * H, 2 * W, Cp)
+            geoms.append(None)
+            packed.append(None)
+            continue
         g = _geom(ly, shape)
         wt = wph = wq = None
         if ly.kind == "conv":
@@ -168,6 +187,10 @@ def stack_forward(layers, x, params, want_grad=True, norms=None):
     cur = x
     pre, bn_saved = [None] * len(layers), [None] * len(layers)
     for i, (ly, (w, b)) in enumerate(zip(layers, params)):
+        if ly.resamples:
+            cur = ew.pool2x2(cur) if ly.kind == "pool" else ew.upsample2x2(cur)
+            outs.append(cur)
+            continue
         g, (wp, wt, wph, wq) = geoms[i], packed[i]
         nm = norms[i]
         seen = (g.N, g.Ti, g.Hi, g.Wi) if ly.kind == "conv" else (g.N, g.To, g.Ho, g.Wo)
@@ -217,7 +240,8 @@ def _bn_backward(ly, nm, gp, y, bn_saved):
 
 def stack_backward(layers, x, outs, saved, grad_out, need_input_grad=False):
     """grad_out: dL/d(outs[-1]) (post-activation).  Returns (grad_x or None, [(dw, db)], [(dgamma, dbeta)]); db is None for
-    a normalised layer, and the last list holds the layers with trainable norms in stack order."""
+    a normalised layer, (dw, db) is (None, None) for a pool / upsample layer, and the last list holds the layers with trainable
+    norms in stack order."""
     geoms, packed, norms, pre, bn_saved = saved
     n = len(layers)
     # g_pre of the last layer
@@ -226,7 +250,7 @@ def stack_backward(layers, x, outs, saved, grad_out, need_input_grad=False):
         gpre = ew.tanh_bwd(grad_out, outs[-1])
     elif last.act == "sigmoid":
         gpre = ew.sigmoid_bwd(grad_out, outs[-1])
-    elif last.act == "relu":
+    elif last.act in ("relu", "leaky"):
         raise L.LvtError("a ReLU-terminated stack is not used by the reference architectures")
     else:
         gpre = grad_out
@@ -238,7 +262,27 @@ def stack_backward(layers, x, outs, saved, grad_out, need_input_grad=False):
     norm_grads = [None] * n
     gx = None
     for i in range(n - 1, -1, -1):
-        ly, g, (wp, wt, wph, wq) = layers[i], geoms[i], packed[i]
+        ly = layers[i]
+        if ly.resamples:
+            # the dual kernel, with the activation backward of the layer in front folded in
+            grads[i] = (None, None)
+            if i == 0 and not need_input_grad:
+                break
+            prev = layers[i - 1] if i > 0 else None
+            if (i - 1) in res_user or (prev is not None and prev.act in ("tanh", "sigmoid")):
+                raise L.LvtError("a pool / upsample layer follows conv + (Leaky)ReLU layers only")
+            mask = outs[i - 1] if (prev is not None and prev.act in ("relu", "leaky")) else None
+            leaky = prev is not None and prev.act == "leaky"
+            if ly.kind == "pool":
+                gin = ew.upsample2x2(gpres[i], 0.25, mask=mask, leaky=leaky)
+            else:
+                gin = ew.pool2x2(gpres[i], 1.0, mask=mask, leaky=leaky)
+            if i > 0:
+                gpres[i - 1] = gin
+            else:
+                gx = gin
+            continue
+        g, (wp, wt, wph, wq) = geoms[i], packed[i]
         inp = outs[i - 1] if i > 0 else x
         gp = gpres[i]
         if norms[i] is not None:
@@ -266,13 +310,14 @@ def stack_backward(layers, x, outs, saved, grad_out, need_input_grad=False):
             break
         prev = layers[i - 1] if i > 0 else None
         res = gpres[res_user[i - 1]] if (i - 1) in res_user else None
-        mask = outs[i - 1] if (prev is not None and prev.act == "relu") else None
+        mask = outs[i - 1] if (prev is not None and prev.act in ("relu", "leaky")) else None
+        lk = L.EPI_LEAKY_MASK if (prev is not None and prev.act == "leaky") else 0
         if prev is not None and prev.act in ("tanh", "sigmoid"):
             raise L.LvtError("%s is only supported on the last layer of a stack" % prev.act)
         if ly.kind == "conv":
-            gin = G.conv_bwd_data(g, gp, wp, res=res, mask=mask, wt=wt, wph=wph)
+            gin = G.conv_bwd_data(g, gp, wp, res=res, mask=mask, flags=lk, wt=wt, wph=wph)
         else:
-            gin = G.conv_fwd(g, gp, wp, res=res, mask=mask, wq=wq)
+            gin = G.conv_fwd(g, gp, wp, res=res, mask=mask, flags=lk, wq=wq)
         if i > 0:
             gpres[i - 1] = gin
         else:

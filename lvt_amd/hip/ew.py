@@ -67,6 +67,38 @@ def sigmoid_bwd(g, y):
     return out
 
 
+def mask_flags(mask, leaky):
+    """Epilogue flags of a (Leaky)ReLU-backward mask: 0 without one, EPI_MASK, or EPI_MASK | EPI_LEAKY_MASK."""
+    if mask is None:
+        return 0
+    return L.EPI_MASK | (L.EPI_LEAKY_MASK if leaky else 0)
+
+
+def _resample(fn, name, x, out_hw, scale, mask, leaky):
+    L.require(x, mask)
+    N, H, W, Cp = x.shape[0], x.shape[-3], x.shape[-2], x.shape[-1]
+    if x.numel() != N * H * W * Cp:
+        raise L.LvtError("%s: frames only (N, 1, H, W, C) or (N, H, W, C), got %s" % (name, tuple(x.shape)))
+    out = torch.empty(tuple(x.shape[:-3]) + out_hw + (Cp,), dtype=torch.float32, device=x.device)
+    if mask is not None and tuple(mask.shape) != tuple(out.shape):
+        raise L.LvtError("%s: the mask must have the output's shape %s, got %s" % (name, tuple(out.shape), tuple(mask.shape)))
+    L.check(fn(L.ptr(x), N, H, W, Cp, float(scale), L.ptr(mask), mask_flags(mask, leaky), L.ptr(out), L.out_amax(out),
+               L.stream_ptr()), name)
+    return out
+
+
+def pool2x2(x, scale=0.25, mask=None, leaky=False):
+    """(N[,1],H,W,Cp) -> (N[,1],H/2,W/2,Cp): scale * the sum of every 2x2 window.  0.25: AvgPool2d(2); 1: the backward of the
+    nearest upsample.  mask (the output's shape): times (mask > 0), or (mask > 0 ? 1 : 0.2) with `leaky`.  H, W even."""
+    return _resample(L.lib().lvt_pool2x2, "lvt_pool2x2", x, (x.shape[-3] // 2, x.shape[-2] // 2), scale, mask, leaky)
+
+
+def upsample2x2(x, scale=1.0, mask=None, leaky=False):
+    """(N[,1],H,W,Cp) -> (N[,1],2H,2W,Cp): every pixel repeated 2x2, times scale.  1: Upsample(scale_factor=2); 0.25: the backward
+    of the average pool.  mask as for pool2x2."""
+    return _resample(L.lib().lvt_upsample2x2, "lvt_upsample2x2", x, (2 * x.shape[-3], 2 * x.shape[-2]), scale, mask, leaky)
+
+
 def axpy(x, alpha=1.0, alpha_dev=None, add=None):
     L.require(x, alpha_dev, add)
     out = torch.empty_like(x)

@@ -45,7 +45,7 @@ def finalize(C, Cp, gamma, beta, running_mean, running_var, stats=None, nranks=1
 
 
 def apply(y, scale, shift, res=None, act=0):
-    """act(y * scale + shift (+ res)); act: 0, binding.EPI_RELU, binding.EPI_TANH or binding.EPI_SIGMOID | binding.epi_pad(n)
+    """act(y * scale + shift (+ res)); act: 0, binding.EPI_RELU, binding.EPI_LEAKY, binding.EPI_TANH or binding.EPI_SIGMOID | binding.epi_pad(n)
     (the last n channels are zero pads and stay 0).  Reports max |out| (f16x2 mode)."""
     L.require(y, res)
     M, Cp = _rows(y)

@@ -33,7 +33,7 @@ class _ConvStackFn(torch.autograd.Function):
                                                            need_input_grad=ctx.needs_input_grad[0])
         flat = []
         for i, (dw, db) in enumerate(grads):
-            flat.append(dw.view(ctx.shapes[2 * i]))
+            flat.append(dw.view(ctx.shapes[2 * i]) if dw is not None else None)        # (None: a pool / upsample layer)
             flat.append(db.contiguous().view(ctx.shapes[2 * i + 1]) if db is not None else None)
         for dgamma, dbeta in norm_grads:
             flat += [dgamma, dbeta]
@@ -101,9 +101,14 @@ def out_activation_module(name):
 
 def act_after(nxt):
     """Activation the plan folds into the layer whose output the module `nxt` consumes: an explicit ReLU or a ResBlock
-    (whose first op is an in-place ReLU) rectifies it, a trailing Tanh / Sigmoid is the stack's output activation."""
+    (whose first op is an in-place ReLU) rectifies it, a LeakyReLU(0.2) does so with its slope, a trailing Tanh / Sigmoid is
+    the stack's output activation."""
     if isinstance(nxt, (nn.ReLU, ResBlock)):
         return "relu"
+    if isinstance(nxt, nn.LeakyReLU):
+        if nxt.negative_slope != 0.2:
+            raise NotImplementedError("LeakyReLU slope %r: the kernels implement 0.2 only" % (nxt.negative_slope,))
+        return "leaky"
     if isinstance(nxt, nn.Tanh):
         return "tanh"
     if isinstance(nxt, nn.Sigmoid):
@@ -186,6 +191,42 @@ def split_norm(m):
 def is_conv(m, cls):
     """m is a `cls` layer, plain or normalised."""
     return isinstance(m, cls) or (isinstance(m, nn.Sequential) and len(m) == 2 and isinstance(m[0], cls))
+
+
+def plain_plan(layers):
+    """Plan of a Sequential of 3x3-style convolutions (plain or normalised), LeakyReLU / ReLU, AvgPool2d(2), Upsample(2) and an
+    optional output activation -- the ConvEncoder / ConvDecoder families.  -> (plan, owners, norms): one convnet.Layer per conv,
+    pool and upsample; owners[i] the conv module of layer i (None for a pool / upsample), norms as run_stack takes them."""
+    Layer = convnet.Layer
+    mods = list(layers)
+    plan, owners, norms = [], [], []
+    for i, m in enumerate(mods):
+        nxt = mods[i + 1] if i + 1 < len(mods) else None
+        if is_conv(m, nn.Conv2d):
+            conv, nm, kind = split_norm(m)
+            k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
+            plan.append(Layer("conv", (1, k, k), (1, s, s), (0, p, p), conv.in_channels, conv.out_channels,
+                              act=act_after(nxt), norm=kind))
+            owners.append(conv)
+            norms.append(nm)
+        elif isinstance(m, (nn.AvgPool2d, nn.Upsample)):
+            if isinstance(m, nn.AvgPool2d):
+                ok, kind = m.kernel_size == 2 and m.stride == 2 and m.padding == 0, "pool"
+            else:
+                ok, kind = m.scale_factor == 2 and m.mode == "nearest" and m.size is None, "up"
+            if not ok or not plan:
+                raise NotImplementedError("only AvgPool2d(2) / nearest Upsample(scale_factor=2) behind a convolution: %r" % (m,))
+            plan.append(Layer.resample(kind, plan[-1].cout))
+            owners.append(None)
+            norms.append(None)
+        elif not isinstance(m, (nn.LeakyReLU, nn.ReLU, nn.Tanh, nn.Sigmoid)):
+            raise NotImplementedError("no plan for %r" % (m,))
+    return plan, owners, (norms if any(n is not None for n in norms) else None)
+
+
+def plan_params(owners):
+    """[(weight, bias)] of a plan's layers for run_stack; (None, None) for the parameter-less ones."""
+    return [(m.weight, m.bias) if m is not None else (None, None) for m in owners]
 
 
 class ResBlock(nn.Module):
