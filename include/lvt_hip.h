@@ -33,7 +33,7 @@ extern "C" {
 #define LVT_ENODEVICE   (-4)   /* no gfx950 device visible                             */
 
 const char *lvt_last_error(void);
-int lvt_version(void);          /* 660 = leaky activation / mask, 2x2 pool and upsample (ABI changes are listed in INTEGRATION.md) */
+int lvt_version(void);          /* 670 = pixel shuffle / unshuffle by 2 (ABI changes are listed in INTEGRATION.md) */
 /* Device probe: name, CU count, clock (kHz), HBM bytes.  Returns LVT_ENODEVICE without a GPU. */
 int lvt_device_info(char *name, int name_len, int *cus, int *clock_khz, long long *hbm_bytes);
 
@@ -671,6 +671,21 @@ int lvt_pool2x2(const float *x, int N, int H, int W, int Cp, float scale, const 
                 float *out_amax, void *stream);
 int lvt_upsample2x2(const float *x, int N, int H, int W, int Cp, float scale, const float *mask, int mask_flags, float *out,
                     float *out_amax, void *stream);
+
+/* ---- pixel shuffle by 2 and its inverse, channels-last (ABI 670; csrc/shuffle.hip).  nn.PixelShuffle(2) of
+ * vidgen/modeling/generator/resdecoder.py:106,109 with the activation behind it, and its backward.  fp32, 16-byte aligned;
+ * every element touched once; 16-byte accesses on the coarse side, 4-byte accesses (256 consecutive bytes per wave) on the fine
+ * side.  Cp = C rounded up to a multiple of 4.
+ *   lvt_pixel_shuffle2  : x (N, H, W, 4 C) -> out (N, 2H, 2W, Cp), out[n,2h+i,2w+j,c] = act(x[n,h,w,4c+2i+j]) for c < C (torch's
+ *                         channel order); channels C..Cp-1 of out are stored as 0 under every act.  act is EXACTLY one of 0,
+ *                         LVT_EPI_RELU, LVT_EPI_TANH, LVT_EPI_SIGMOID (anything else, LVT_EPI_PAD bits included: LVT_EINVAL -- C is
+ *                         an argument, the kernel knows its pads).  act 0 and RELU move bits unchanged.
+ *   lvt_pixel_unshuffle2: g (N, 2H, 2W, Cp) -> out (N, H, W, 4 C), out[n,h,w,4c+2i+j] = g[n,2h+i,2w+j,c]; channels C..Cp-1 of g are
+ *                         ignored.  No mask: the layer in front of a shuffle has no activation.
+ * N, H, W are the extents of the COARSE side in both calls.  N, H, W, C <= 0, a null or misaligned pointer: LVT_EINVAL, nothing
+ * is written.  out_amax (nullable): max |out| as in lvt_pool2x2.  No floating-point atomics: two runs give the same bits. */
+int lvt_pixel_shuffle2(const float *x, int N, int H, int W, int C, int act, float *out, float *out_amax, void *stream);
+int lvt_pixel_unshuffle2(const float *g, int N, int H, int W, int C, float *out, float *out_amax, void *stream);
 
 #ifdef __cplusplus
 }

@@ -23,7 +23,7 @@ def epi_pad(n):
         raise ValueError("epi_pad: 0..3 pad channels, got %r" % (n,))
     return n << 24
 CAUSAL_KMAX, CAUSAL_KMIN, CAUSAL_TILE = 1 << 8, 1 << 9, 1 << 10      # causal attention products (include/lvt_hip.h)
-ABI_VERSION = 660           # lvt_version() of the library this module binds (argument lists below)
+ABI_VERSION = 670           # lvt_version() of the library this module binds (argument lists below)
 MATH_F32 = 1 << 16          # per-call arithmetic selectors of the engine entry points (include/lvt_hip.h)
 MATH_F16X2 = 1 << 18
 ONEHOT_DENSE = 1 << 19
@@ -220,6 +220,8 @@ def _declare(lib):
         "lvt_bn_fold": (ci, [P(BnFoldEntry), ci, vp]),
         "lvt_pool2x2": (ci, [vp, ci, ci, ci, ci, cf, vp, ci, vp, vp, vp]),
         "lvt_upsample2x2": (ci, [vp, ci, ci, ci, ci, cf, vp, ci, vp, vp, vp]),
+        "lvt_pixel_shuffle2": (ci, [vp, ci, ci, ci, ci, ci, vp, vp, vp]),
+        "lvt_pixel_unshuffle2": (ci, [vp, ci, ci, ci, ci, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)

@@ -24,6 +24,12 @@ Resampling (Layer.kind "pool" / "up", csrc/resample.hip): parameter-less layers 
 and the gradients are (None, None) / None, so layer indices (res_from, norms) count them.  Each is the other's backward -- pool
 with scale 1 under an upsample, upsample with scale 0.25 under a pool -- and that launch applies the (Leaky)ReLU mask of the layer
 in front, like the data-gradient epilogues of the convolutions.
+
+Pixel shuffle (Layer.kind "shuffle", csrc/shuffle.hip): nn.PixelShuffle(2) with the activation behind it, parameter-less like the
+resampling layers but with an `act` of its own -- ReLU, tanh and sigmoid are elementwise and commute with the permutation, so
+outs[i] stays the post-activation output of layer i and the backward of that activation happens where it does for a convolution
+(the head for tanh / sigmoid, the mask in the next layer's data-gradient epilogue for ReLU).  The convolution in front carries no
+activation; the shuffle's own backward is the inverse permutation.
 """
 
 import torch
@@ -36,8 +42,9 @@ from . import norm as BN
 class Layer:
     """One conv / ConvTranspose layer of a stack.
 
-    kind: "conv" | "convT" | "pool" | "up" (the last two: AvgPool2d(2) / Upsample(scale_factor=2); no parameters, no activation,
-    no norm, cin == cout; see Layer.resample).  For convT the geometry is that of the equivalent forward conv whose
+    kind: "conv" | "convT" | "pool" | "up" | "shuffle" ("pool" / "up": AvgPool2d(2) / Upsample(scale_factor=2); no parameters, no
+    activation, no norm, cin == cout; see Layer.resample.  "shuffle": PixelShuffle(2); no parameters, no norm, cin == 4 cout, act
+    "" | "relu" | "tanh" | "sigmoid"; see Layer.shuffle).  For convT the geometry is that of the equivalent forward conv whose
     backward-data IS this layer (Ci = out channels of the ConvTranspose, Co = its in channels).
     act: "" | "relu" | "leaky" (LeakyReLU(0.2)) | "tanh" | "sigmoid" (the last two on the last layer of a stack only).  res_from: index of an earlier
     output added before the activation (-1: none).  ci_real / co_real: channel counts of the torch-layout weight (pads excluded).
@@ -49,7 +56,7 @@ class Layer:
         self.kind, self.kernel, self.stride, self.pad = kind, kernel, stride, pad
         self.cin, self.cout, self.act, self.res_from = cin, cout, act, res_from
         self.norm = norm
-        self.resamples = kind in ("pool", "up")
+        self.resamples = kind in ("pool", "up", "shuffle")
 
     @staticmethod
     def pad4(c):
@@ -59,6 +66,19 @@ class Layer:
     def resample(cls, kind, channels):
         assert kind in ("pool", "up")
         return cls(kind, None, None, None, channels, channels)
+
+    @classmethod
+    def shuffle(cls, channels, act=""):
+        """PixelShuffle(2) to `channels` channels, followed by `act`."""
+        assert act in ("", "relu", "tanh", "sigmoid")
+        return cls("shuffle", None, None, None, 4 * channels, channels, act=act)
+
+    def resampled_shape(self, shape):
+        """Channels-last output shape of a parameter-less layer."""
+        N, T, H, W, Cp = shape
+        if self.kind == "pool":
+            return (N, T, H // 2, W // 2, Cp)
+        return (N, T, 2 * H, 2 * W, Cp if self.kind == "up" else Layer.pad4(self.cout))
 
 
 def _geom(layer, x_shape):
@@ -157,8 +177,7 @@ def stack_forward(layers, x, params, want_grad=True, norms=None):
     shape = tuple(x.shape)
     for i, (ly, (w, b)) in enumerate(zip(layers, params)):
         if ly.resamples:
-            N, T, H, W, Cp = shape
-            shape = (N, T, H // 2, W // 2, Cp) if ly.kind == "pool" else (N, T, 2 * H, 2 * W, Cp)
+            shape = ly.resampled_shape(shape)
             geoms.append(None)
             packed.append(None)
             continue
@@ -188,7 +207,10 @@ def stack_forward(layers, x, params, want_grad=True, norms=None):
     pre, bn_saved = [None] * len(layers), [None] * len(layers)
     for i, (ly, (w, b)) in enumerate(zip(layers, params)):
         if ly.resamples:
-            cur = ew.pool2x2(cur) if ly.kind == "pool" else ew.upsample2x2(cur)
+            if ly.kind == "shuffle":
+                cur = ew.pixel_shuffle2(cur, ly.cout, ly.act)
+            else:
+                cur = ew.pool2x2(cur) if ly.kind == "pool" else ew.upsample2x2(cur)
             outs.append(cur)
             continue
         g, (wp, wt, wph, wq) = geoms[i], packed[i]
@@ -240,7 +262,7 @@ def _bn_backward(ly, nm, gp, y, bn_saved):
 
 def stack_backward(layers, x, outs, saved, grad_out, need_input_grad=False):
     """grad_out: dL/d(outs[-1]) (post-activation).  Returns (grad_x or None, [(dw, db)], [(dgamma, dbeta)]); db is None for
-    a normalised layer, (dw, db) is (None, None) for a pool / upsample layer, and the last list holds the layers with trainable
+    a normalised layer, (dw, db) is (None, None) for a pool / upsample / shuffle layer, and the last list holds the layers with trainable
     norms in stack order."""
     geoms, packed, norms, pre, bn_saved = saved
     n = len(layers)
@@ -269,6 +291,16 @@ def stack_backward(layers, x, outs, saved, grad_out, need_input_grad=False):
             if i == 0 and not need_input_grad:
                 break
             prev = layers[i - 1] if i > 0 else None
+            if ly.kind == "shuffle":
+                # the inverse permutation; this layer's own activation was undone by the head or by the mask of the layer behind
+                if (i - 1) in res_user or (prev is not None and prev.act):
+                    raise L.LvtError("a pixel shuffle must follow a convolution without activation that is no residual source")
+                gin = ew.pixel_unshuffle2(gpres[i], ly.cout)
+                if i > 0:
+                    gpres[i - 1] = gin
+                else:
+                    gx = gin
+                continue
             if (i - 1) in res_user or (prev is not None and prev.act in ("tanh", "sigmoid")):
                 raise L.LvtError("a pool / upsample layer follows conv + (Leaky)ReLU layers only")
             mask = outs[i - 1] if (prev is not None and prev.act in ("relu", "leaky")) else None

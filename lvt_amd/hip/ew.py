@@ -99,6 +99,48 @@ def upsample2x2(x, scale=1.0, mask=None, leaky=False):
     return _resample(L.lib().lvt_upsample2x2, "lvt_upsample2x2", x, (2 * x.shape[-3], 2 * x.shape[-2]), scale, mask, leaky)
 
 
+_SHUFFLE_ACTS = {"": 0, "relu": L.EPI_RELU, "tanh": L.EPI_TANH, "sigmoid": L.EPI_SIGMOID}
+
+
+def _frames(name, x):
+    if x.dim() in (4, 5):
+        N, H, W, Cx = x.shape[0], x.shape[-3], x.shape[-2], x.shape[-1]
+        if x.numel() == N * H * W * Cx:
+            return N, H, W, Cx
+    raise L.LvtError("%s: frames only (N, 1, H, W, C) or (N, H, W, C), got %s" % (name, tuple(x.shape)))
+
+
+def pixel_shuffle2(x, C, act=""):
+    """(N[,1],H,W,4C) -> (N[,1],2H,2W,pad4(C)): nn.PixelShuffle(2) followed by `act` ("" | "relu" | "tanh" | "sigmoid");
+    out[n,2h+i,2w+j,c] = act(x[n,h,w,4c+2i+j]), the pad channels C.. exact zeros under every act.  `act` may also be the epilogue
+    flags of convnet._act_flag: the pad count that rides on a sigmoid flag is dropped, the kernel knows its pads from C."""
+    L.require(x)
+    N, H, W, Cx = _frames("lvt_pixel_shuffle2", x)
+    if C <= 0 or Cx != 4 * C:
+        raise L.LvtError("lvt_pixel_shuffle2: %d channels in, 4 * C = %d expected" % (Cx, 4 * C))
+    if isinstance(act, str):
+        if act not in _SHUFFLE_ACTS:
+            raise L.LvtError("lvt_pixel_shuffle2: act %r is none of %s" % (act, sorted(_SHUFFLE_ACTS)))
+        flag = _SHUFFLE_ACTS[act]
+    else:
+        flag = act & ~L.epi_pad(3)
+    out = torch.empty(tuple(x.shape[:-3]) + (2 * H, 2 * W, (C + 3) // 4 * 4), dtype=torch.float32, device=x.device)
+    L.check(L.lib().lvt_pixel_shuffle2(L.ptr(x), N, H, W, C, flag, L.ptr(out), L.out_amax(out), L.stream_ptr()), "lvt_pixel_shuffle2")
+    return out
+
+
+def pixel_unshuffle2(g, C):
+    """(N[,1],2H,2W,pad4(C)) -> (N[,1],H,W,4C): the inverse (and backward) of pixel_shuffle2; the pad channels of g are ignored."""
+    L.require(g)
+    N, H2, W2, Cp = _frames("lvt_pixel_unshuffle2", g)
+    if C <= 0 or Cp != (C + 3) // 4 * 4 or H2 % 2 or W2 % 2:
+        raise L.LvtError("lvt_pixel_unshuffle2: (.., %d, %d, %d) is not the shuffle of C = %d channels" % (H2, W2, Cp, C))
+    out = torch.empty(tuple(g.shape[:-3]) + (H2 // 2, W2 // 2, 4 * C), dtype=torch.float32, device=g.device)
+    L.check(L.lib().lvt_pixel_unshuffle2(L.ptr(g), N, H2 // 2, W2 // 2, C, L.ptr(out), L.out_amax(out), L.stream_ptr()),
+            "lvt_pixel_unshuffle2")
+    return out
+
+
 def axpy(x, alpha=1.0, alpha_dev=None, add=None):
     L.require(x, alpha_dev, add)
     out = torch.empty_like(x)

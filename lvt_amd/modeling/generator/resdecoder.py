@@ -1,9 +1,12 @@
-"""Residual conv decoder (reference: vidgen/modeling/generator/resdecoder.py:25-75).
+"""Residual conv decoders (reference: vidgen/modeling/generator/resdecoder.py:25-129).
 
-    Conv(k3 p1), n x ResBlock, ReLU, ConvT(k4 s2 p1)+ReLU, ConvT(k4 s2 p1) [, tanh | sigmoid]
+    ResDecoder         Conv(k3 p1), n x ResBlock, ReLU, ConvT(k4 s2 p1)+ReLU, ConvT(k4 s2 p1) [, tanh | sigmoid]
+    ResShuffleDecoder  Conv(k3 p1), n x ResBlock, ReLU, Conv(k3 p1)+PixelShuffle(2)+ReLU, Conv(k3 p1)+PixelShuffle(2) [, tanh | sigmoid]
 
 ConvTranspose layers run as the backward-data form of the implicit-GEMM engine, decomposed by
-output stride phase so that no matrix-core work is spent on structurally-zero taps.
+output stride phase so that no matrix-core work is spent on structurally-zero taps.  The sub-pixel decoder's 3x3 convolutions are
+the frame-resident kernels of the trunk at 16x16 and 32x32; each PixelShuffle is one streaming launch that also applies the
+activation behind it (hip/convnet.py, Layer.kind "shuffle").  The two classes share everything but the upscaling tail.
 """
 from torch import nn
 
@@ -13,8 +16,9 @@ from .build import GENERATOR_REGISTRY
 from .generator import Generator
 
 
-@GENERATOR_REGISTRY.register()
-class ResDecoder(Generator):
+class _ResTrunkDecoder(Generator):
+    """Trunk, output activation, plan and forward of both decoders; `_upscale` is the tail between them."""
+
     @classmethod
     def from_config(cls, cfg, **kwargs):
         g = cfg.MODEL.GENERATOR
@@ -31,15 +35,7 @@ class ResDecoder(Generator):
         mods = [nl(nn.Conv2d(in_channels, nf, 3, 1, 1), norm)]
         mods += [convstack.ResBlock(nf, res_channels, norm) for _ in range(n_layers)]
         mods.append(nn.ReLU(True))
-        if stride == 4:
-            # the last ConvTranspose is never normalised (resdecoder.py:55-59)
-            mods += [nl(nn.ConvTranspose2d(nf, nf // 2, 4, 2, 1), norm), nn.ReLU(True),
-                     nn.ConvTranspose2d(nf // 2, out_channels, 4, 2, 1)]
-        elif stride == 2:
-            # ... except at stride 2, where it is the only one and the reference normalises it (resdecoder.py:60-63)
-            mods += [nl(nn.ConvTranspose2d(nf, out_channels, 4, 2, 1), norm)]
-        else:
-            raise ValueError
+        mods += self._upscale(nf, out_channels, norm, stride)
         out_act = convstack.out_activation_module(out_activation)
         if out_act is not None:
             mods.append(out_act)
@@ -71,14 +67,51 @@ class ResDecoder(Generator):
                                   res_from=src, norm=k1))
                 owners.append(c1)
                 norms.append(n1)
+            elif isinstance(m, nn.PixelShuffle):
+                if m.upscale_factor != 2 or not plan or plan[-1].cout % 4:
+                    raise NotImplementedError("only PixelShuffle(2) behind a convolution to 4 C channels: %r" % (m,))
+                plan.append(Layer.shuffle(plan[-1].cout // 4, act=act))
+                owners.append(None)
+                norms.append(None)
         self._owners = owners
         self._norms = norms if any(n is not None for n in norms) else None      # NORM "": the plain stack, as before
         return plan
 
     def forward_cl(self, z_cl):
         """(N,1,h,w,Cin) channels-last -> (N,1,4h,4w,Cout_pad4)."""
-        return convstack.run_stack(z_cl, self._plan, [(m.weight, m.bias) for m in self._owners], self._norms)
+        return convstack.run_stack(z_cl, self._plan, convstack.plan_params(self._owners), self._norms)
 
     def forward(self, z):
         y = self.forward_cl(convstack._LayoutIn.apply(z))
         return convstack._LayoutOut.apply(y, self.out_channels)
+
+
+@GENERATOR_REGISTRY.register()
+class ResDecoder(_ResTrunkDecoder):
+    @staticmethod
+    def _upscale(nf, out_channels, norm, stride):
+        nl = convstack.norm_layer
+        if stride == 4:
+            # the last ConvTranspose is never normalised (resdecoder.py:55-59)
+            return [nl(nn.ConvTranspose2d(nf, nf // 2, 4, 2, 1), norm), nn.ReLU(True),
+                    nn.ConvTranspose2d(nf // 2, out_channels, 4, 2, 1)]
+        if stride == 2:
+            # ... except at stride 2, where it is the only one and the reference normalises it (resdecoder.py:60-63)
+            return [nl(nn.ConvTranspose2d(nf, out_channels, 4, 2, 1), norm)]
+        raise ValueError
+
+
+@GENERATOR_REGISTRY.register()
+class ResShuffleDecoder(_ResTrunkDecoder):
+    """Sub-pixel variant (resdecoder.py:78-129): each ConvTranspose2d(4, 2, 1) becomes Conv2d(3, 1, 1) to four times the channels
+    and PixelShuffle(2).  Which convolutions are normalised follows ResDecoder's rule."""
+
+    @staticmethod
+    def _upscale(nf, out_channels, norm, stride):
+        nl = convstack.norm_layer
+        if stride == 4:
+            return [nl(nn.Conv2d(nf, nf // 2 * 4, 3, 1, 1), norm), nn.PixelShuffle(2), nn.ReLU(True),
+                    nn.Conv2d(nf // 2, out_channels * 4, 3, 1, 1), nn.PixelShuffle(2)]
+        if stride == 2:
+            return [nl(nn.Conv2d(nf, out_channels * 4, 3, 1, 1), norm), nn.PixelShuffle(2)]
+        raise ValueError
