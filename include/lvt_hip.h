@@ -33,7 +33,7 @@ extern "C" {
 #define LVT_ENODEVICE   (-4)   /* no gfx950 device visible                             */
 
 const char *lvt_last_error(void);
-int lvt_version(void);          /* 670 = pixel shuffle / unshuffle by 2 (ABI changes are listed in INTEGRATION.md) */
+int lvt_version(void);          /* 680 = gradient clipping in the optimizer steps (ABI changes are listed in INTEGRATION.md) */
 /* Device probe: name, CU count, clock (kHz), HBM bytes.  Returns LVT_ENODEVICE without a GPU. */
 int lvt_device_info(char *name, int name_len, int *cus, int *clock_khz, long long *hbm_bytes);
 
@@ -602,6 +602,39 @@ int lvt_adam_step(const lvt_opt_entry *entries, int n, float beta1, float beta2,
 /* s0 = square_avg, s1 = momentum_buffer.                                                                */
 int lvt_rmsprop_step(const lvt_opt_entry *entries, int n, float alpha, float eps, float momentum,
                      void *stream);
+
+/* ---- gradient clipping inside the optimizer steps (ABI 680; torch.nn.utils.clip_grad_norm_ / clip_grad_value_ without their
+ * host read and without a pass that rewrites the gradients).  Three stages on one stream, no host synchronisation:
+ *   1. lvt_grad_sqnorm: sum of squares of every gradient, one fp64 partial per 16384-element chunk (plain stores);
+ *   2. lvt_grad_clip_coef: the partials added in a fixed order in fp64 -> a device record;
+ *   3. the *_step_scaled entries read the record: the gradient is multiplied by `coef` (one fp32 rounding, as a gradient
+ *      clipped in place has) before weight decay and the moment updates, or nothing at all is stored when `skip` is set.
+ * Squares and sums are fp64 from the first product on: any finite fp32 gradient gives a finite, non-zero sum.  A NaN or inf
+ * element makes its partial, and with it the sum, NaN or inf: that is the non-finiteness test.  No floating-point atomics;
+ * partials and record depend only on the entry list and the gradients' bits.  The gradients are never written.             */
+typedef struct { const float *g; long long n; } lvt_grad_entry;      /* one gradient: device pointer, element count */
+typedef struct {
+    float norm;      /* (float)sqrt(sum g^2) over every entry                                                       */
+    float coef;      /* (float)min(1, max_norm / (norm + 1e-6)), evaluated in fp64; 0 when the sum is not finite    */
+    int skip;        /* 1 when the sum is not finite (the scaled steps then store nothing), else 0                  */
+    int reserved;    /* written as 0                                                                                */
+} lvt_clip_record;
+/* number of partials lvt_grad_sqnorm writes for these entries (host-side arithmetic: sum of ceil(n_i / 16384)); -1 on a bad entry */
+long long lvt_grad_sqnorm_partials(const lvt_grad_entry *entries, int n);
+/* `entries` is a HOST array (64 per launch, by value); partials[c] for chunk c, chunks numbered consecutively over the whole
+ * list; n_partials must equal lvt_grad_sqnorm_partials(entries, n).                                                         */
+int lvt_grad_sqnorm(const lvt_grad_entry *entries, int n, double *partials, long long n_partials, void *stream);
+/* one workgroup: record <- (norm, coef, skip) of the n_partials partials; *skipped (int64 device counter, nullable) += skip.
+ * max_norm > 0.  record is 16-byte aligned.                                                                              */
+int lvt_grad_clip_coef(const double *partials, long long n_partials, float max_norm, lvt_clip_record *record,
+                       long long *skipped, void *stream);
+/* lvt_adam_step / lvt_rmsprop_step on the gradient g' = clamp(g * coef): `gscale` (nullable device record) supplies coef and
+ * skip, `clamp` = c > 0 limits every element of g * coef to [-c, c] (a NaN stays a NaN), 0 = off.  At least one of the two
+ * must be given.  With skip set, p, s0 and s1 keep their bits.  The unscaled entries above launch their own kernels.       */
+int lvt_adam_step_scaled(const lvt_opt_entry *entries, int n, float beta1, float beta2, float eps, int step,
+                         const lvt_clip_record *gscale, float clamp, void *stream);
+int lvt_rmsprop_step_scaled(const lvt_opt_entry *entries, int n, float alpha, float eps, float momentum,
+                            const lvt_clip_record *gscale, float clamp, void *stream);
 
 /* ---- batch normalisation of the conv stacks (nn.BatchNorm2d, NaiveSyncBatchNorm, FrozenBatchNorm2d of the reference's
  * vidgen/layers/batch_norm.py; csrc/norm.hip).  Activations are channels-last (M = N*T*H*W rows, Cp channels), Cp = C

@@ -3,7 +3,8 @@
 // turns an optimizer step into hundreds of tiny launches (394 tensors x ~6 kernels for DSFVT).  Here up to
 // 64 tensors travel BY VALUE in the kernel arguments (no table upload, no host sync) and each workgroup
 // updates one 16K-element chunk.  Math follows torch.optim.Adam / torch.optim.RMSprop (non-amsgrad,
-// non-centered) operation by operation.
+// non-centered) operation by operation.  The *_scaled entries (ABI 680) run the same update on a clipped gradient; the global
+// norm behind the clip coefficient comes from lvt_grad_sqnorm / lvt_grad_clip_coef below.
 #include "lvt_common.h"
 #include <math.h>
 
@@ -29,14 +30,32 @@ __device__ __forceinline__ bool opt_vec_ok(const LvtOptEntry &e, long long lo) {
     return (a & 15) == 0 && (e.n & 3) == 0 && (lo & 3) == 0;
 }
 
-__global__ __launch_bounds__(256) void lvt_adam_kernel(const OptArgs a, float beta1, float beta2, float eps,
-                                                       float bc1, float bc2_sqrt) {
+// The gradient an update sees under clipping (ABI 680): g * coef, then the clamp.  The product is rounded on its own, as a
+// gradient clipped in place is -- contracting it into the weight-decay sum behind it would round once instead of twice and
+// break bit equality with the unscaled kernel at coef == 1.  The comparisons keep a NaN a NaN, as torch.clamp does.
+__device__ __forceinline__ float clipped_grad(float g, float coef, float clamp) {
+#pragma clang fp contract(off)
+    g = g * coef;
+    if (clamp > 0.f) g = g < -clamp ? -clamp : (g > clamp ? clamp : g);
+    return g;
+}
+
+// SCALED = false is the body of lvt_adam_step as it always was (gscale and clamp are dead); SCALED = true: lvt_adam_step_scaled.
+template <bool SCALED>
+__device__ __forceinline__ void adam_body(const OptArgs &a, float beta1, float beta2, float eps, float bc1, float bc2_sqrt,
+                                          const lvt_clip_record *gscale, float clamp) {
+    float coef = 1.f;
+    if (SCALED && gscale) {
+        if (gscale->skip) return;           // non-finite gradient norm: no store, p / s0 / s1 keep their bits
+        coef = gscale->coef;
+    }
     const int t = find_tensor(a, blockIdx.x);
     const LvtOptEntry e = a.e[t];
     const long long lo = (long long)(blockIdx.x - a.chunk_prefix[t]) * OPT_CHUNK;
     const long long hi = min(e.n, lo + OPT_CHUNK);
     const float step = e.lr / bc1;
     auto upd = [&](float g, float p, float &m, float &v) -> float {
+        if (SCALED) g = clipped_grad(g, coef, clamp);
         if (e.wd != 0.f) g += e.wd * p;
         m = m + (1.f - beta1) * (g - m);                                   // exp_avg.lerp_(grad, 1 - beta1)
         v = beta2 * v + (1.f - beta2) * g * g;                             // mul_(beta2).addcmul_(g, g, 1 - beta2)
@@ -61,12 +80,31 @@ __global__ __launch_bounds__(256) void lvt_adam_kernel(const OptArgs a, float be
     }
 }
 
-__global__ __launch_bounds__(256) void lvt_rmsprop_kernel(const OptArgs a, float alpha, float eps, float momentum) {
+__global__ __launch_bounds__(256) void lvt_adam_kernel(const OptArgs a, float beta1, float beta2, float eps,
+                                                       float bc1, float bc2_sqrt) {
+    adam_body<false>(a, beta1, beta2, eps, bc1, bc2_sqrt, nullptr, 0.f);
+}
+
+__global__ __launch_bounds__(256) void lvt_adam_scaled_kernel(const OptArgs a, float beta1, float beta2, float eps,
+                                                              float bc1, float bc2_sqrt, const lvt_clip_record *gscale,
+                                                              float clamp) {
+    adam_body<true>(a, beta1, beta2, eps, bc1, bc2_sqrt, gscale, clamp);
+}
+
+template <bool SCALED>
+__device__ __forceinline__ void rmsprop_body(const OptArgs &a, float alpha, float eps, float momentum,
+                                             const lvt_clip_record *gscale, float clamp) {
+    float coef = 1.f;
+    if (SCALED && gscale) {
+        if (gscale->skip) return;
+        coef = gscale->coef;
+    }
     const int t = find_tensor(a, blockIdx.x);
     const LvtOptEntry e = a.e[t];
     const long long lo = (long long)(blockIdx.x - a.chunk_prefix[t]) * OPT_CHUNK;
     const long long hi = min(e.n, lo + OPT_CHUNK);
     auto upd = [&](float g, float p, float &sq, float &buf) -> float {
+        if (SCALED) g = clipped_grad(g, coef, clamp);
         if (e.wd != 0.f) g += e.wd * p;
         sq = alpha * sq + (1.f - alpha) * g * g;
         const float avg = sqrtf(sq) + eps;
@@ -92,6 +130,66 @@ __global__ __launch_bounds__(256) void lvt_rmsprop_kernel(const OptArgs a, float
         e.p[i] = upd(e.g[i], e.p[i], sq, buf);
         e.s0[i] = sq;
         if (mom) e.s1[i] = buf;
+    }
+}
+
+__global__ __launch_bounds__(256) void lvt_rmsprop_kernel(const OptArgs a, float alpha, float eps, float momentum) {
+    rmsprop_body<false>(a, alpha, eps, momentum, nullptr, 0.f);
+}
+
+__global__ __launch_bounds__(256) void lvt_rmsprop_scaled_kernel(const OptArgs a, float alpha, float eps, float momentum,
+                                                                 const lvt_clip_record *gscale, float clamp) {
+    rmsprop_body<true>(a, alpha, eps, momentum, gscale, clamp);
+}
+
+// ---- global gradient norm (ABI 680) ------------------------------------------------------------------------------------------
+// Sum of 256 per-thread fp64 values of a workgroup in a fixed tree: xor butterfly inside each wave, the four wave sums added in
+// wave order by thread 0 (whose return value is the sum).  A NaN or inf anywhere comes out as NaN or inf.
+__device__ __forceinline__ double block_sum_f64(double v, double *scratch) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return scratch[0] + scratch[1] + scratch[2] + scratch[3];
+}
+
+// one workgroup per 16384-element chunk, like the steps; only e.g and e.n of the table are set
+__global__ __launch_bounds__(256) void lvt_grad_sqnorm_kernel(const OptArgs a, double *partials) {
+    __shared__ double scratch[4];
+    const int t = find_tensor(a, blockIdx.x);
+    const LvtOptEntry e = a.e[t];
+    const long long lo = (long long)(blockIdx.x - a.chunk_prefix[t]) * OPT_CHUNK;
+    const long long hi = min(e.n, lo + OPT_CHUNK);
+    double acc = 0.0;
+    auto sq = [&](float g) { const double d = (double)g; acc += d * d; };
+    if (opt_vec_ok(e, lo)) {
+        for (long long i = lo + 4 * threadIdx.x; i < hi; i += 1024) {
+            const float4 g4 = *reinterpret_cast<const float4 *>(e.g + i);
+            sq(g4.x); sq(g4.y); sq(g4.z); sq(g4.w);
+        }
+    } else {
+        for (long long i = lo + threadIdx.x; i < hi; i += 256) sq(e.g[i]);
+    }
+    const double total = block_sum_f64(acc, scratch);
+    if (threadIdx.x == 0) partials[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(256) void lvt_grad_clip_coef_kernel(const double *partials, long long n, float max_norm,
+                                                                 lvt_clip_record *record, long long *skipped) {
+    __shared__ double scratch[4];
+    double acc = 0.0;
+    for (long long i = threadIdx.x; i < n; i += 256) acc += partials[i];
+    const double total = block_sum_f64(acc, scratch);
+    if (threadIdx.x == 0) {
+        const bool finite = fabs(total) < __builtin_inf();            // false for NaN and for +inf
+        const double norm = sqrt(total);
+        lvt_clip_record r;
+        r.norm = (float)norm;
+        r.coef = finite ? (float)fmin(1.0, (double)max_norm / (norm + 1e-6)) : 0.f;
+        r.skip = finite ? 0 : 1;
+        r.reserved = 0;
+        *record = r;
+        if (!finite && skipped) *skipped += 1;
     }
 }
 
@@ -137,4 +235,77 @@ extern "C" int lvt_rmsprop_step(const LvtOptEntry *host, int n, float alpha, flo
     return for_each_group(host, n, [&](const OptArgs &a, int blocks) {
         hipLaunchKernelGGL(lvt_rmsprop_kernel, dim3(blocks), dim3(256), 0, s, a, alpha, eps, momentum);
     });
+}
+
+#define REQUIRE_CLIP_ARGS(name)                                                                                              \
+    LVT_REQUIRE(clamp >= 0.f && clamp < __builtin_inff() && (gscale || clamp > 0.f) && (((uintptr_t)gscale) & 15) == 0,      \
+                name ": needs a 16-byte aligned gscale record, a finite clamp > 0, or both")
+
+extern "C" int lvt_adam_step_scaled(const LvtOptEntry *host, int n, float beta1, float beta2, float eps, int step,
+                                    const lvt_clip_record *gscale, float clamp, void *stream) {
+    LVT_REQUIRE(host && n > 0 && step > 0, "adam_step_scaled: bad args");
+    REQUIRE_CLIP_ARGS("adam_step_scaled");
+    hipStream_t s = (hipStream_t)stream;
+    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+    return for_each_group(host, n, [&](const OptArgs &a, int blocks) {
+        hipLaunchKernelGGL(lvt_adam_scaled_kernel, dim3(blocks), dim3(256), 0, s, a, beta1, beta2, eps, (float)bc1,
+                           (float)sqrt(bc2), gscale, clamp);
+    });
+}
+
+extern "C" int lvt_rmsprop_step_scaled(const LvtOptEntry *host, int n, float alpha, float eps, float momentum,
+                                       const lvt_clip_record *gscale, float clamp, void *stream) {
+    LVT_REQUIRE(host && n > 0, "rmsprop_step_scaled: bad args");
+    REQUIRE_CLIP_ARGS("rmsprop_step_scaled");
+    hipStream_t s = (hipStream_t)stream;
+    return for_each_group(host, n, [&](const OptArgs &a, int blocks) {
+        hipLaunchKernelGGL(lvt_rmsprop_scaled_kernel, dim3(blocks), dim3(256), 0, s, a, alpha, eps, momentum, gscale, clamp);
+    });
+}
+
+extern "C" long long lvt_grad_sqnorm_partials(const lvt_grad_entry *host, int n) {
+    if (!host || n <= 0) return -1;
+    long long chunks = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!host[i].g || host[i].n <= 0 || (((uintptr_t)host[i].g) & 3)) return -1;
+        chunks += lvt_cdiv(host[i].n, OPT_CHUNK);
+    }
+    return chunks;
+}
+
+extern "C" int lvt_grad_sqnorm(const lvt_grad_entry *host, int n, double *partials, long long n_partials, void *stream) {
+    LVT_REQUIRE(host && n > 0 && partials && (((uintptr_t)partials) & 7) == 0, "grad_sqnorm: bad args");
+    const long long need = lvt_grad_sqnorm_partials(host, n);
+    LVT_REQUIRE(need > 0, "grad_sqnorm: bad entry (null or misaligned gradient, or no elements)");
+    LVT_REQUIRE(need == n_partials, "grad_sqnorm: %lld partials for entries that need %lld", n_partials, need);
+    hipStream_t s = (hipStream_t)stream;
+    long long done = 0;                                   // chunks of the launches before this one
+    for (int base = 0; base < n; base += OPT_MAXT) {
+        OptArgs a = {};
+        a.n = (n - base) < OPT_MAXT ? (n - base) : OPT_MAXT;
+        long long blocks = 0;
+        for (int i = 0; i < a.n; ++i) {
+            a.e[i].g = host[base + i].g;
+            a.e[i].n = host[base + i].n;
+            a.chunk_prefix[i] = (int)blocks;
+            blocks += lvt_cdiv(a.e[i].n, OPT_CHUNK);
+        }
+        LVT_REQUIRE(blocks < (1ll << 31), "grad_sqnorm: too many chunks in one launch");
+        a.chunk_prefix[a.n] = (int)blocks;
+        hipLaunchKernelGGL(lvt_grad_sqnorm_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, partials + done);
+        LVT_CHECK_LAUNCH("grad_sqnorm kernel");
+        done += blocks;
+    }
+    return LVT_OK;
+}
+
+extern "C" int lvt_grad_clip_coef(const double *partials, long long n_partials, float max_norm, lvt_clip_record *record,
+                                  long long *skipped, void *stream) {
+    LVT_REQUIRE(partials && n_partials > 0 && record && (((uintptr_t)record) & 15) == 0 && (((uintptr_t)skipped) & 7) == 0,
+                "grad_clip_coef: bad args");
+    LVT_REQUIRE(max_norm > 0.f && max_norm < __builtin_inff(), "grad_clip_coef: max_norm must be positive and finite");
+    hipLaunchKernelGGL(lvt_grad_clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n_partials, max_norm,
+                       record, skipped);
+    LVT_CHECK_LAUNCH("grad_clip_coef kernel");
+    return LVT_OK;
 }

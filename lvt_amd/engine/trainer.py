@@ -6,6 +6,10 @@ train_loop.py:112-133, defaults.py:273-310), minus its per-step host synchronisa
   * losses are kept on the device; they are fetched (one D2H copy) only every `log_period` iterations, where the
     finiteness check of `_detect_anomaly` is also applied.  The reference does `.item()` + a gloo gather of a
     pickled dict every step, which serialises the ranks.
+  * SOLVER.CLIP_GRADIENTS (solver/clip.py): on an iteration that steps, the data-parallel reduction is joined and ONE clipper over
+    all optimizers prepares the step (global norm / skip flag on the device, or the clamp); the accumulated gradient is
+    clipped once.  No host synchronisation: `grad_norm` and `skipped_steps` ride in the D2H copy of the losses at `log_period`.
+    Disabled (the default), the trainer holds no clipper and the sequence above is unchanged.
   * checkpoints: one Checkpointer per sub-network, `model_{iter:07d}.pth` / `model_final.pth`, rank 0 only.
 """
 import logging
@@ -13,6 +17,7 @@ import time
 
 import torch
 
+from ..solver.build import build_grad_clipper
 from ..utils import comm
 from ..utils.checkpoint import PeriodicCheckpointer
 from ..utils.events import EventStorage
@@ -24,6 +29,7 @@ class Trainer:
         self.optimizers, self.checkpointers = model.configure_optimizers_and_checkpointers()
         if comm.get_world_size() > 1:
             model.wrap_parallel(device_ids=[comm.get_local_rank()], broadcast_buffers=False)
+        self.clipper = build_grad_clipper(cfg, self.optimizers)       # None unless SOLVER.CLIP_GRADIENTS.ENABLED
         model.train()
         self.start_iter, self.max_iter = 0, cfg.SOLVER.MAX_ITER
         self.accumulation_steps = cfg.SOLVER.ACCUMULATION_STEPS
@@ -43,6 +49,9 @@ class Trainer:
         losses = sum(loss_dict.values())
         losses.backward()
         if (self.iter + 1) % self.accumulation_steps == 0:
+            if self.clipper is not None:
+                self.model.finish_gradient_sync()          # the norm is taken over the REDUCED gradients: the same on every rank
+                self.clipper.prepare()
             for item in self.optimizers:
                 item["optimizer"].step()
             for item in self.optimizers:
@@ -58,10 +67,19 @@ class Trainer:
             for self.iter in range(self.start_iter, max_iter):
                 last = self.run_step()
                 if (self.iter + 1) % self.log_period == 0 or self.iter == max_iter - 1:
-                    vals = {k: float(v.detach()) for k, v in last.items()}          # the only D2H sync
+                    clip = {}
+                    if self.clipper is None or self.clipper.norm is None:
+                        vals = {k: float(v.detach()) for k, v in last.items()}          # the only D2H sync
+                    else:       # losses, gradient norm and skip counter in ONE copy (a skipped step's norm is inf / nan: not an anomaly)
+                        extra = [self.clipper.norm, self.clipper.skipped]
+                        host = torch.stack([v.detach().reshape(()).double() for v in list(last.values()) + extra]).tolist()
+                        vals = dict(zip(last, host))
+                        clip = {"grad_norm": host[-2], "skipped_steps": host[-1]}
                     if not all(torch.isfinite(torch.tensor(list(vals.values())))):
                         raise FloatingPointError("Loss became infinite or NaN at iteration={}! {}".format(self.iter, vals))
                     storage.put_scalars(**vals)
+                    storage.put_scalars(smoothing_hint=False, **clip)
+                    vals.update(clip)
                     if comm.is_main_process():
                         dt = (time.perf_counter() - t0) / (self.iter + 1 - self.start_iter)
                         self.logger.info("iter %d  %s  %.4f s/it", self.iter,

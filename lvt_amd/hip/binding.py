@@ -23,7 +23,7 @@ def epi_pad(n):
         raise ValueError("epi_pad: 0..3 pad channels, got %r" % (n,))
     return n << 24
 CAUSAL_KMAX, CAUSAL_KMIN, CAUSAL_TILE = 1 << 8, 1 << 9, 1 << 10      # causal attention products (include/lvt_hip.h)
-ABI_VERSION = 670           # lvt_version() of the library this module binds (argument lists below)
+ABI_VERSION = 680           # lvt_version() of the library this module binds (argument lists below)
 MATH_F32 = 1 << 16          # per-call arithmetic selectors of the engine entry points (include/lvt_hip.h)
 MATH_F16X2 = 1 << 18
 ONEHOT_DENSE = 1 << 19
@@ -105,6 +105,14 @@ class AmaxIO(C.Structure):
 class OptEntry(C.Structure):
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("s0", C.c_void_p), ("s1", C.c_void_p),
                 ("n", C.c_longlong), ("lr", C.c_float), ("wd", C.c_float)]
+
+
+class GradEntry(C.Structure):
+    """lvt_grad_entry (include/lvt_hip.h): one gradient of the global-norm pass."""
+    _fields_ = [("g", C.c_void_p), ("n", C.c_longlong)]
+
+
+CLIP_RECORD_BYTES = 16      # lvt_clip_record: float norm, float coef, int skip, int reserved
 
 
 class ConvGeom(C.Structure):
@@ -211,6 +219,11 @@ def _declare(lib):
         "lvt_xent_bwd": (ci, [vp, vp, cll, cll, ci, cll, ci, cll, vp, vp, vp, cf, vp, vp, vp]),
         "lvt_adam_step": (ci, [P(OptEntry), ci, cf, cf, cf, ci, vp]),
         "lvt_rmsprop_step": (ci, [P(OptEntry), ci, cf, cf, cf, vp]),
+        "lvt_adam_step_scaled": (ci, [P(OptEntry), ci, cf, cf, cf, ci, vp, cf, vp]),
+        "lvt_rmsprop_step_scaled": (ci, [P(OptEntry), ci, cf, cf, cf, vp, cf, vp]),
+        "lvt_grad_sqnorm_partials": (cll, [P(GradEntry), ci]),
+        "lvt_grad_sqnorm": (ci, [P(GradEntry), ci, vp, cll, vp]),
+        "lvt_grad_clip_coef": (ci, [vp, cll, cf, vp, vp, vp]),
         "lvt_bn_workspace_bytes": (sz, [cll, ci]),
         "lvt_bn_stats": (ci, [vp, cll, ci, vp, vp, sz, vp]),
         "lvt_bn_finalize": (ci, [vp, ci, cll, ci, ci, vp, vp, vp, vp, vp, cf, cf, ci, vp, vp, vp, vp]),

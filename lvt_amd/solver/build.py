@@ -8,6 +8,7 @@ from bisect import bisect_right
 import torch
 from torch.optim.lr_scheduler import LambdaLR
 
+from .clip import GradClipper, check_clip_args
 from .fused import FusedAdam, FusedRMSprop
 
 _NORM_TYPES = (torch.nn.BatchNorm1d, torch.nn.BatchNorm2d, torch.nn.BatchNorm3d, torch.nn.SyncBatchNorm,
@@ -43,6 +44,18 @@ def build_optimizer(model, cfg, suffix=""):
         return cls(params, lr, alpha=s.RMSPROP["ALPHA" + suffix], weight_decay=wd,
                    momentum=s.RMSPROP["MOMENTUM" + suffix])
     raise ValueError("Unknown optimizer: {}".format(s.OPTIMIZER_NAME))
+
+
+def build_grad_clipper(cfg, optimizers):
+    """SOLVER.CLIP_GRADIENTS (detectron2's keys) -> a GradClipper over ALL the given optimizers (the objects, or the
+    {"optimizer": ...} items the meta-architectures return), or None when disabled.  A bad setting is a ValueError whether
+    or not clipping is enabled."""
+    c = cfg.SOLVER.CLIP_GRADIENTS
+    check_clip_args(c.CLIP_TYPE, c.CLIP_VALUE, c.NORM_TYPE)
+    if not c.ENABLED:
+        return None
+    return GradClipper([o["optimizer"] if isinstance(o, dict) else o for o in optimizers], c.CLIP_TYPE, c.CLIP_VALUE,
+                       c.NORM_TYPE)
 
 
 def _warmup_factor(method, it, warmup_iters, warmup_factor):

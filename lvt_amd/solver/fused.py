@@ -4,6 +4,10 @@ Same constructor arguments, param_groups / state layout (state keys `step`, `exp
 for Adam; `step`, `square_avg`, `momentum_buffer` for RMSprop) and update rule as torch.optim.Adam /
 torch.optim.RMSprop, so checkpoints and LR schedulers are interchangeable.  Parameters that are not on a
 GPU fall back to raising: there is no CPU path in this package.
+
+Gradient clipping (solver/clip.py) happens inside the step kernels: `set_grad_clip` hands the NEXT `step()` a device record
+with the clip coefficient and the skip flag of the global gradient norm, and / or an elementwise clamp.  `step()` consumes it:
+a step that was handed nothing calls the unclipped entry points.  `p.grad` is never rewritten.
 """
 import ctypes as C
 
@@ -24,6 +28,20 @@ def _entries(items):
 
 
 class _FusedBase(Optimizer):
+    _clip = None            # (record tensor or None, clamp) for the next step(): set_grad_clip
+
+    def set_grad_clip(self, record=None, clamp=0.0):
+        """The next `step()` (and only that one) updates with clamp(g * coef) in the place of every gradient g: `record` is the
+        device lvt_clip_record GradClipper filled (coef, and skip: a set flag makes the step store nothing), `clamp` = c > 0
+        limits every element to [-c, c], 0 is off."""
+        if record is None and not clamp > 0:
+            raise ValueError("set_grad_clip needs a record, a clamp > 0, or both")
+        self._clip = (record, float(clamp))
+
+    def _take_clip(self):
+        clip, self._clip = self._clip, None
+        return clip
+
     def zero_grad(self, set_to_none=True):
         """torch semantics; gradients living in a data-parallel bucket (engine/grad_reducer.py) are always DROPPED
         (`.grad = None`: `set_to_none=False` is not honoured for them -- a zeroed view that stays attached would make autograd
@@ -79,6 +97,7 @@ class FusedAdam(_FusedBase):
             st["step"] = 0
             st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
             st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        clip = self._take_clip()
         for step, items in self._collect(make).items():
             # groups may differ in betas/eps in principle; batch by (betas, eps)
             batches = {}
@@ -88,8 +107,12 @@ class FusedAdam(_FusedBase):
                                                     group["weight_decay"]))
             for (betas, eps), ents in batches.items():
                 arr = _entries(ents)
-                L.check(L.lib().lvt_adam_step(arr, len(ents), betas[0], betas[1], eps, step, L.stream_ptr()),
-                        "lvt_adam_step")
+                if clip is None:
+                    L.check(L.lib().lvt_adam_step(arr, len(ents), betas[0], betas[1], eps, step, L.stream_ptr()),
+                            "lvt_adam_step")
+                else:
+                    L.check(L.lib().lvt_adam_step_scaled(arr, len(ents), betas[0], betas[1], eps, step, L.ptr(clip[0]),
+                                                         clip[1], L.stream_ptr()), "lvt_adam_step_scaled")
         L.bump_epoch()          # parameters were rewritten through raw pointers: cached max |.| records are stale
         return loss
 
@@ -108,6 +131,7 @@ class FusedRMSprop(_FusedBase):
             st["square_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
             if group["momentum"] > 0:
                 st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        clip = self._take_clip()
         for step, items in self._collect(make).items():
             batches = {}
             for p, g, st, group in items:
@@ -116,6 +140,10 @@ class FusedRMSprop(_FusedBase):
                                                     group["weight_decay"]))
             for (alpha, eps, mom), ents in batches.items():
                 arr = _entries(ents)
-                L.check(L.lib().lvt_rmsprop_step(arr, len(ents), alpha, eps, mom, L.stream_ptr()), "lvt_rmsprop_step")
+                if clip is None:
+                    L.check(L.lib().lvt_rmsprop_step(arr, len(ents), alpha, eps, mom, L.stream_ptr()), "lvt_rmsprop_step")
+                else:
+                    L.check(L.lib().lvt_rmsprop_step_scaled(arr, len(ents), alpha, eps, mom, L.ptr(clip[0]), clip[1],
+                                                            L.stream_ptr()), "lvt_rmsprop_step_scaled")
         L.bump_epoch()
         return loss
