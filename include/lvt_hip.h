@@ -381,6 +381,24 @@ int lvt_vq_ema_accumulate(const long long *idx, const float *z, long long rows, 
  * D == 64: any KC; other D up to 256: KC up to 2048.                                                 */
 int lvt_vq_ema_finalize(const float *stats, int num, int D, int KC, float decay, float eps,
                         float *running_size, float *running_sum, float *weight, void *stream);
+/* Codebook restart (MODEL.CODEBOOK.RESTART; additive under ABI 680; csrc/vq_restart.hip).  D: multiple of 16 in 16..256, KC:
+ * multiple of 64 in 64..2048, any num.  No atomics, fixed order.
+ * lvt_vq_restart_candidates: cand[num][KC][D]; code k of group g draws the global row
+ *   r = lo + (hi > lo ? h % (hi - lo) : 0),  lo = k R / KC,  hi = (k + 1) R / KC,  R = world * rows_local,
+ *   h = splitmix64's finaliser of  seed ^ pass[0] * 0x9E3779B97F4A7C15 ^ (i << 32 | k),  i = shared_index ? 0 : g,
+ * and cand[g][k][:] = z[r - rank * rows_local][g*D .. g*D+D) where this rank owns r (global row = rank * rows_local + local),
+ * zeros elsewhere: a SUM over ranks gathers the candidates exactly.  pass: device counter, read only.
+ * lvt_vq_ema_finalize_restart: the update of lvt_vq_ema_finalize (codes that are not restarted: bit for bit), then every code
+ *   whose count in `stats` is 0 and whose updated running_size < threshold becomes weight = cand, running_sum = cand *
+ *   threshold, running_size = threshold.  health[num][3] = (perplexity exp(-sum p ln p) of the counts, accumulated in fp64;
+ *   codes with updated running_size < threshold before any restart; codes restarted); restarts_total[num] += restarted;
+ *   pass[0] += 1.  threshold 0 restarts nothing (monitoring only); a negative or non-finite one is LVT_EINVAL.            */
+int lvt_vq_restart_candidates(const float *z, long long rows_local, int ldz, int num, int D, int KC, int P, int rank,
+                              int world, unsigned long long seed, const long long *pass, int shared_index, float *cand,
+                              void *stream);
+int lvt_vq_ema_finalize_restart(const float *stats, const float *cand, int num, int D, int KC, float decay, float eps,
+                                float threshold, float *running_size, float *running_sum, float *weight, float *health,
+                                long long *restarts_total, long long *pass, void *stream);
 
 /* ---- boundary layout conversion + input (de)normalisation (ae.py:32-37,151-168; K12) --------------
  * to_channels_last : in [B][C][R] -> out [B][R][ldo] (columns >= C zero); mode 1: (x - a[c]) / s[c]

@@ -10,6 +10,8 @@ train_loop.py:112-133, defaults.py:273-310), minus its per-step host synchronisa
     all optimizers prepares the step (global norm / skip flag on the device, or the clamp); the accumulated gradient is
     clipped once.  No host synchronisation: `grad_norm` and `skipped_steps` ride in the D2H copy of the losses at `log_period`.
     Disabled (the default), the trainer holds no clipper and the sequence above is unchanged.
+  * MODEL.CODEBOOK.RESTART: `codebook_perplexity`, `codebook_dead` and `codebook_restarts` (device scalars of the quantiser's
+    health record) ride in the same copy.  Off (the default), nothing changes.
   * checkpoints: one Checkpointer per sub-network, `model_{iter:07d}.pth` / `model_final.pth`, rank 0 only.
 """
 import logging
@@ -68,13 +70,22 @@ class Trainer:
                 last = self.run_step()
                 if (self.iter + 1) % self.log_period == 0 or self.iter == max_iter - 1:
                     clip = {}
-                    if self.clipper is None or self.clipper.norm is None:
+                    clipping = self.clipper is not None and self.clipper.norm is not None
+                    health = getattr(self.model, "codebook_health", None)
+                    health = health() if health is not None else None
+                    if not clipping and health is None:
                         vals = {k: float(v.detach()) for k, v in last.items()}          # the only D2H sync
                     else:       # losses, gradient norm and skip counter in ONE copy (a skipped step's norm is inf / nan: not an anomaly)
-                        extra = [self.clipper.norm, self.clipper.skipped]
+                        names, extra = [], []
+                        if health is not None:      # (always finite; logged like the clipper's pair, outside the losses)
+                            names += ["codebook_perplexity", "codebook_dead", "codebook_restarts"]
+                            extra += list(health)
+                        if clipping:
+                            names += ["grad_norm", "skipped_steps"]
+                            extra += [self.clipper.norm, self.clipper.skipped]
                         host = torch.stack([v.detach().reshape(()).double() for v in list(last.values()) + extra]).tolist()
                         vals = dict(zip(last, host))
-                        clip = {"grad_norm": host[-2], "skipped_steps": host[-1]}
+                        clip = dict(zip(names, host[len(last):]))
                     if not all(torch.isfinite(torch.tensor(list(vals.values())))):
                         raise FloatingPointError("Loss became infinite or NaN at iteration={}! {}".format(self.iter, vals))
                     storage.put_scalars(**vals)

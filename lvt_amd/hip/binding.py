@@ -176,6 +176,8 @@ def _declare(lib):
         "lvt_vq_ema_workspace_bytes": (sz, [cll, ci, ci, ci]),
         "lvt_vq_ema_accumulate": (ci, [vp, vp, cll, ci, ci, ci, ci, ci, vp, vp, sz, vp]),
         "lvt_vq_ema_finalize": (ci, [vp, ci, ci, ci, cf, cf, vp, vp, vp, vp]),
+        "lvt_vq_restart_candidates": (ci, [vp, cll, ci, ci, ci, ci, ci, ci, ci, C.c_ulonglong, vp, ci, vp, vp]),
+        "lvt_vq_ema_finalize_restart": (ci, [vp, vp, ci, ci, ci, cf, cf, cf, vp, vp, vp, vp, vp, vp, vp]),
         "lvt_to_channels_last": (ci, [vp, ci, ci, cll, ci, ci, vp, vp, vp, vp, vp]),
         "lvt_to_channels_first": (ci, [vp, ci, ci, cll, ci, ci, vp, vp, cf, cf, vp, vp]),
         "lvt_reduce_workspace_bytes": (sz, []),

@@ -61,13 +61,21 @@ def gather(idx, codebooks):
     return out
 
 
-def ema_accumulate(idx, z, K):
-    """-> stats (num, K, D+1): per-code sums and counts of the rows assigned to each code."""
+def ema_accumulate(idx, z, K, out=None):
+    """-> stats (num, K, D+1): per-code sums and counts of the rows assigned to each code.
+    out: a contiguous (num, K, D+1) float32 tensor to write them into (a view of the buffer that one collective sums:
+    restart_buffer) instead of a fresh one."""
     L.require(idx, z)
     n, num, P = idx.shape
     rows, ldz = z.shape
     D = ldz // num
-    stats = torch.empty(num, K, D + 1, dtype=torch.float32, device=z.device)
+    if out is None:
+        stats = torch.empty(num, K, D + 1, dtype=torch.float32, device=z.device)
+    else:
+        L.require(out)
+        if out.shape != (num, K, D + 1) or out.dtype != torch.float32 or out.device != z.device:
+            raise L.LvtError("ema_accumulate: out must be a float32 (%d, %d, %d) tensor on %s" % (num, K, D + 1, z.device))
+        stats = out
     lib = L.lib()
     nws = lib.lvt_vq_ema_workspace_bytes(rows, num, D, K)
     ws = L.workspace(nws, z.device, "ema")
@@ -81,4 +89,57 @@ def ema_finalize(stats, running_size, running_sum, weight, decay=0.99, eps=1e-5)
     num, K, D = weight.shape
     L.check(L.lib().lvt_vq_ema_finalize(L.ptr(stats), num, D, K, decay, eps, L.ptr(running_size),
                                         L.ptr(running_sum), L.ptr(weight), L.stream_ptr()), "lvt_vq_ema_finalize")
+    L.drop_amax(weight)         # rewritten in place behind torch's back
+
+
+# ---- codebook restart (MODEL.CODEBOOK.RESTART; csrc/vq_restart.hip) --------------------------------------------------------
+_M64 = (1 << 64) - 1
+
+
+def _mix64(z):
+    """splitmix64's finaliser."""
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def restart_row(seed, pass_, i, k, R, K):
+    """Global row (0 <= r < R) whose sub-vector code k of codebook i takes if it is restarted in pass `pass_`: the plain-Python
+    statement of rst_row in csrc/vq_restart.hip.  Code k draws from its own stratum [k R // K, (k + 1) R // K) of the R rows,
+    so distinct codes get distinct rows whenever R >= K; an empty stratum (R < K) yields its lower end."""
+    h = _mix64((seed ^ (pass_ * 0x9E3779B97F4A7C15) ^ (i << 32 | k)) & _M64)
+    lo, hi = k * R // K, (k + 1) * R // K
+    return lo + (h % (hi - lo) if hi > lo else 0)
+
+
+def restart_buffer(num, K, D, device):
+    """One flat float32 buffer [stats (num, K, D+1) | cand (num, K, D)] -> (flat, stats view, cand view): a data-parallel pass
+    sums it with ONE collective, which completes the statistics and gathers the candidates (all ranks but a row's owner
+    contribute zeros)."""
+    ns = num * K * (D + 1)
+    flat = torch.empty(ns + num * K * D, dtype=torch.float32, device=device)
+    return flat, flat[:ns].view(num, K, D + 1), flat[ns:].view(num, K, D)
+
+
+def restart_candidates(z, cand, P, rank, world, seed, pass_counter, shared_index=False):
+    """cand (num, K, D) <- for every code the sub-vector of the row it would be re-seeded from (restart_row), where this rank
+    owns that row, zeros elsewhere.  z (rows_local, ldz) channels-last; pass_counter: int64 device scalar (read only)."""
+    L.require(z, cand, pass_counter)
+    rows, ldz = z.shape
+    num, K, D = cand.shape
+    L.check(L.lib().lvt_vq_restart_candidates(L.ptr(z), rows, ldz, num, D, K, P, rank, world, seed, L.ptr(pass_counter),
+                                              int(bool(shared_index)), L.ptr(cand), L.stream_ptr()),
+            "lvt_vq_restart_candidates")
+
+
+def ema_finalize_restart(stats, cand, running_size, running_sum, weight, threshold, health, restarts_total, pass_counter,
+                         decay=0.99, eps=1e-5):
+    """ema_finalize, then the restart rule; writes health (num, 3) float32 = (perplexity, dead, restarted), adds `restarted` to
+    restarts_total (num,) int64 and advances pass_counter (int64 scalar)."""
+    L.require(stats, cand, running_size, running_sum, weight, health, restarts_total, pass_counter)
+    num, K, D = weight.shape
+    L.check(L.lib().lvt_vq_ema_finalize_restart(L.ptr(stats), L.ptr(cand), num, D, K, decay, eps, threshold,
+                                                L.ptr(running_size), L.ptr(running_sum), L.ptr(weight), L.ptr(health),
+                                                L.ptr(restarts_total), L.ptr(pass_counter), L.stream_ptr()),
+            "lvt_vq_ema_finalize_restart")
     L.drop_amax(weight)         # rewritten in place behind torch's back

@@ -27,6 +27,9 @@ class VQVAEModel(AutoEncoderModel):
             self.codebook = DVQEmbedding(cb.NUM, cb.SIZE, cb.DIM, self.use_codebook_ema)
         if self.use_codebook_ema:
             self._set_requires_grad(self.codebook.parameters(), False)
+        if cb.RESTART.ENABLED:
+            # (the un-offset config seed: every rank must draw the same rows)
+            self.codebook.enable_restart(cb.RESTART.THRESHOLD, max(cfg.SEED, 0))
         self.pixel_loss = PixelLoss(cfg)
         self.beta = cb.BETA
         self.to(self.device)
@@ -56,6 +59,11 @@ class VQVAEModel(AutoEncoderModel):
                 for t in self.codebook._flat():
                     if t is not None:
                         dist.broadcast(t, 0)
+
+    def codebook_health(self):
+        """Device scalars (codebook_perplexity, codebook_dead, codebook_restarts) of the last train pass, or None when
+        MODEL.CODEBOOK.RESTART is off (engine/trainer.py logs them)."""
+        return self.codebook.health_scalars()
 
     def _generator_parameters(self):
         params = super()._generator_parameters()

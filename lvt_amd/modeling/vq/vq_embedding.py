@@ -14,6 +14,8 @@ Deliberate, documented deviations:
     `straight_through_cl(z, defer=True)` starts the collective asynchronously right after the statistics kernel and returns;
     `finish_ema()` joins it, applies the EMA update and gathers z_q_bar for the commitment loss -- after the decoder forward
     has been enqueued (meta_arch/vqvae.py).  Same arithmetic, same order of updates as the reference (vq_embedding.py:46-59).
+  * `enable_restart` (MODEL.CODEBOOK.RESTART; the reference has nothing like it, off by default): dead codes are re-seeded from
+    encoder rows of the pass inside the finalize launch, and a health record is kept (_RestartMixin).
 """
 import torch
 from torch import nn
@@ -21,6 +23,7 @@ from torch import nn
 from ...hip import binding as L
 from ...hip import ew, vq
 from ...layers.all_reduce import all_reduce_sum_async_
+from ...utils import comm
 from .. import convstack
 
 SUPPORTED_GEOMETRY = ("sub-vector width DIM / NUM: a multiple of 16 from 16 to 256 (product quantiser, DVQEmbedding) or "
@@ -47,6 +50,68 @@ def check_geometry(num, K, D, single=False):
         raise NotImplementedError("unsupported codebook SIZE=%d; supported: %s" % (K, SUPPORTED_GEOMETRY))
 
 
+class _RestartMixin:
+    """Codebook restart (MODEL.CODEBOOK.RESTART) for the two quantisers.  Off until `enable_restart` is called; then,
+    in train mode, every pass gathers one candidate row per code next to the EMA statistics (same collective) and the finalize
+    launch re-seeds the codes that won no row and whose running_size fell below the threshold.  The pass counter, the health
+    record and the cumulative restart counter are NON-persistent buffers: the state-dict keys stay the reference's, and a
+    resumed run draws a different stream of rows."""
+
+    _restart = None                # (threshold, seed) once enabled
+
+    def enable_restart(self, threshold=1.0, seed=0):
+        """threshold: a code is dead when its updated running_size is below it (0.0: monitoring only); seed: of the draw, the
+        same on every rank."""
+        threshold = float(threshold)
+        if not self.ema:
+            raise ValueError("codebook restart needs CODEBOOK.EMA: a trained codebook has no running_size")
+        if not (0.0 <= threshold < float("inf")):
+            raise ValueError("codebook restart: THRESHOLD must be finite and >= 0 (got %r)" % (threshold,))
+        ngroups = getattr(self, "groups", self.num)       # (SingleVQEmbedding: one record per 64-d group, all equal)
+        dev = self._flat()[0].device
+        self.register_buffer("restart_pass", torch.zeros(1, dtype=torch.int64, device=dev), persistent=False)
+        self.register_buffer("restart_health", torch.zeros(ngroups, 3, device=dev), persistent=False)
+        self.register_buffer("restart_total", torch.zeros(ngroups, dtype=torch.int64, device=dev), persistent=False)
+        self._restart = (threshold, max(int(seed), 0))
+
+    @property
+    def restart_enabled(self):
+        return self._restart is not None
+
+    def _restart_now(self):
+        """This pass gathers candidates and finalizes with the restart kernel: enabled, and in train mode."""
+        return self._restart is not None and self.training
+
+    def _accumulate(self, idx, z2d, P, shared_index):
+        """EMA statistics of a pass (+ the restart candidates behind them in ONE buffer) and the start of their all-reduce
+        -> (stats, work, cand or None)."""
+        if not self._restart_now():
+            stats = vq.ema_accumulate(idx, z2d, self.K)
+            return stats, all_reduce_sum_async_(stats), None
+        num = idx.shape[1]
+        flat, stats, cand = vq.restart_buffer(num, self.K, z2d.shape[1] // num, z2d.device)
+        vq.ema_accumulate(idx, z2d, self.K, out=stats)
+        vq.restart_candidates(z2d, cand, P, comm.get_rank(), comm.get_world_size(), self._restart[1], self.restart_pass,
+                              shared_index=shared_index)
+        return stats, all_reduce_sum_async_(flat), cand
+
+    def _finalize(self, stats, cand, rsize, rsum, w):
+        if cand is None:
+            vq.ema_finalize(stats, rsize, rsum, w, self.decay, self.eps)
+        else:
+            vq.ema_finalize_restart(stats, cand, rsize, rsum, w, self._restart[0], self.restart_health, self.restart_total,
+                                    self.restart_pass, self.decay, self.eps)
+
+    def health_scalars(self):
+        """(perplexity: mean over codebooks, dead: sum, restarts: cumulative sum) of the last finalized train pass as device
+        scalars -- no host synchronisation; None unless restart is enabled."""
+        if self._restart is None:
+            return None
+        n = self.num                                      # (the groups of a single codebook carry the same record: take one)
+        h = self.restart_health[:n].double()
+        return h[:, 0].mean(), h[:, 1].sum(), self.restart_total[:n].sum().double()
+
+
 class VQEmbedding(nn.Module):
     """One codebook: parameter / buffer container (vq_embedding.py:9-21)."""
 
@@ -71,10 +136,10 @@ class _StraightThroughFn(torch.autograd.Function):
         idx = vq.nearest(z2d, w, P)
         z_q_st = vq.gather(idx, w)                       # from the PRE-update codebook
         stats = work = None
+        cand = None
         if owner.ema:
-            stats = vq.ema_accumulate(idx, z2d, owner.K)
-            work = all_reduce_sum_async_(stats)
-        owner._pending = (idx, stats, work)
+            stats, work, cand = owner._accumulate(idx, z2d, P, False)
+        owner._pending = (idx, stats, work, cand)
         ctx.mark_non_differentiable(idx)
         return z_q_st, idx
 
@@ -111,10 +176,11 @@ class _SingleStraightThroughFn(torch.autograd.Function):
         idx_g = owner._group_idx(idx, P)
         z_q_st = vq.gather(idx_g, owner._grouped(w))             # from the PRE-update codebook
         stats = work = None
+        cand = None
         if owner.ema:
-            stats = vq.ema_accumulate(idx_g, z2d, owner.K)       # (g, K, 65): the 64-d slices of the sums | the counts
-            work = all_reduce_sum_async_(stats)
-        owner._pending = (idx, idx_g, stats, work)
+            # (g, K, 65): the 64-d slices of the sums | the counts; a restart draws ONE row for all the groups of a code
+            stats, work, cand = owner._accumulate(idx_g, z2d, P, True)
+        owner._pending = (idx, idx_g, stats, work, cand)
         ctx.mark_non_differentiable(idx)
         return z_q_st, idx
 
@@ -140,7 +206,7 @@ class _SingleGatherWithGradFn(torch.autograd.Function):
         return None, None, stats[:, :, :64].permute(1, 0, 2).reshape(o.K, o.D).contiguous()
 
 
-class SingleVQEmbedding(VQEmbedding):
+class SingleVQEmbedding(_RestartMixin, VQEmbedding):
     """`VQEmbedding` used directly as the quantiser: CODEBOOK.NUM == 1, the default of the config tree (config/defaults.py:79,
     meta_arch/vqvae.py:25-27).  Same parameters, buffers and state_dict keys as the reference's class (`embedding.weight`,
     `running_size`, `running_sum`); latents carry no codebook axis: (N, H, W).
@@ -198,14 +264,14 @@ class SingleVQEmbedding(VQEmbedding):
     def finish_ema(self):
         if self._pending is None:
             raise L.LvtError("SingleVQEmbedding.finish_ema without a pending straight_through_cl")
-        idx, idx_g, stats, work = self._pending
+        idx, idx_g, stats, work, cand = self._pending
         self._pending = None
         w = self.embedding.weight
         if stats is not None:
             if work is not None:
                 work.wait()
             wg, rs, rsum = self._grouped(w.data), self._grouped(self.running_size), self._grouped(self.running_sum)
-            vq.ema_finalize(stats, rs, rsum, wg, self.decay, self.eps)
+            self._finalize(stats, cand, rs, rsum, wg)
             with torch.no_grad():
                 w.data.copy_(self._ungrouped(wg))
                 self.running_size.copy_(rs[0])
@@ -238,7 +304,7 @@ class SingleVQEmbedding(VQEmbedding):
         raise ValueError
 
 
-class DVQEmbedding(nn.Module):
+class DVQEmbedding(_RestartMixin, nn.Module):
     def __init__(self, num, K, D, ema):
         super().__init__()
         check_geometry(num, K, D)
@@ -301,13 +367,13 @@ class DVQEmbedding(nn.Module):
         pend = getattr(self, "_pending", None)
         if pend is None:
             raise L.LvtError("DVQEmbedding.finish_ema without a pending straight_through_cl")
-        idx, stats, work = pend
+        idx, stats, work, cand = pend
         self._pending = None
         w, rsize, rsum = self._flat()
         if stats is not None:
             if work is not None:
                 work.wait()
-            vq.ema_finalize(stats, rsize, rsum, w, self.decay, self.eps)
+            self._finalize(stats, cand, rsize, rsum, w)
         if not self.ema:
             # a trained codebook: z_q_bar carries the graph to the `num` weight parameters (vq_embedding.py:61-64); their
             # gradient is the reference's index_add_ of the incoming rows (vq_utils.py:56-63)
