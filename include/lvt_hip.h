@@ -654,6 +654,24 @@ int lvt_adam_step_scaled(const lvt_opt_entry *entries, int n, float beta1, float
 int lvt_rmsprop_step_scaled(const lvt_opt_entry *entries, int n, float alpha, float eps, float momentum,
                             const lvt_clip_record *gscale, float clamp, void *stream);
 
+/* ---- Polyak-averaged weights inside the optimizer steps (an exponential moving average of every parameter, kept by the
+ * launch that writes the parameter).  `ema` is a HOST array of n device pointers: ema[i] is the shadow of entries[i].p and
+ * holds entries[i].n floats.  p, s0 and s1 are updated exactly as by the entries above; then, with the new value p' still in
+ * a register, e <- e + w (p' - e), w = 1 - decay in [0, 1] (the lerp_ form of torch.optim.swa_utils.get_ema_multi_avg_fn).
+ * `gscale` may be NULL and `clamp` 0: both absent run the unclipped update, otherwise the one of the *_scaled entries.  With
+ * gscale->skip set the shadows keep their bits too.  A shadow that is not 16-byte aligned is accessed 4 bytes at a time; the
+ * loop that updates p is chosen by p, g, s0 and s1 alone, as in the entries above, so that p, s0 and s1 never depend on where a
+ * shadow lies (for the same reason the scalar loop of short, ragged or misaligned tensors keeps its instructions and its
+ * threads revisit p right after storing it).  64 tensors and their shadows travel by value per launch.  lvt_opt_entry is
+ * unchanged.                                                                                                                */
+int lvt_adam_step_ema(const lvt_opt_entry *entries, float *const *ema, int n, float beta1, float beta2, float eps, int step,
+                      float w, const lvt_clip_record *gscale, float clamp, void *stream);
+int lvt_rmsprop_step_ema(const lvt_opt_entry *entries, float *const *ema, int n, float alpha, float eps, float momentum,
+                         float w, const lvt_clip_record *gscale, float clamp, void *stream);
+/* exchanges the contents of a[i] and b[i] (counts[i] floats each, disjoint; host arrays of device pointers) in place, 64 pairs
+ * per launch, chunked like the steps.  Calling it twice restores every bit.                                                 */
+int lvt_ema_swap(float *const *a, float *const *b, const long long *counts, int n, void *stream);
+
 /* ---- batch normalisation of the conv stacks (nn.BatchNorm2d, NaiveSyncBatchNorm, FrozenBatchNorm2d of the reference's
  * vidgen/layers/batch_norm.py; csrc/norm.hip).  Activations are channels-last (M = N*T*H*W rows, Cp channels), Cp = C
  * rounded up to 4; the pad channels of every output stay exactly 0.  All reductions are deterministic (row-block partials

@@ -102,6 +102,9 @@ _TABLE = [
     ('SOLVER.CLIP_GRADIENTS.CLIP_TYPE', 'norm'),     # "norm": global 2-norm over all optimizers; "value": elementwise clamp
     ('SOLVER.CLIP_GRADIENTS.CLIP_VALUE', 1.0),
     ('SOLVER.CLIP_GRADIENTS.NORM_TYPE', 2.0),
+    ('SOLVER.MODEL_EMA.ENABLED', False),             # Polyak-averaged weights kept by the fused optimizer steps: solver/ema.py
+    ('SOLVER.MODEL_EMA.DECAY', 0.9999),
+    ('SOLVER.MODEL_EMA.WARMUP', True),               # decay of update t: min(DECAY, (1 + t) / (10 + t))
     ('LOSS.PIXEL.ONN', False),
     ('LOSS.PIXEL.LAMBDA', 1.0),
     ('LOSS.PIXEL.MODE', 'l2'),

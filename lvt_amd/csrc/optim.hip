@@ -40,10 +40,48 @@ __device__ __forceinline__ float clipped_grad(float g, float coef, float clamp) 
     return g;
 }
 
+// Polyak averaging inside the step (lvt_*_step_ema): the table of a launch plus the shadow of every tensor, by value like the
+// table itself.  The kernel-argument segment holds 4 KB; the widest EMA kernel adds nine 4- or 8-byte scalars behind this.
+struct EmaArgs {
+    OptArgs a;
+    float *ema[OPT_MAXT];
+};
+static_assert(sizeof(EmaArgs) + 64 <= 4096, "EmaArgs and the scalars of the EMA kernels must fit the 4 KB of kernel arguments: "
+                                            "carry fewer tensors per launch");
+
+// e + w (p - e): the lerp_ form of torch.optim.swa_utils.get_ema_multi_avg_fn, w = 1 - decay
+__device__ __forceinline__ float ema_follow(float e, float p, float w) { return e + w * (p - e); }
+// Four elements of a shadow behind a float4 of new parameter values.  Which loop a tensor takes is decided by p, g, s0 and s1
+// alone, as without averaging: the scalar and the float4 loop of a step do not round alike (the compiler contracts their
+// multiply-adds differently), so a shadow that picked the loop would change the trajectory of p.  A shadow that is not
+// 16-byte aligned (`vec` false) is read and written 4 bytes at a time instead.
+__device__ __forceinline__ void ema_follow4(float *sh, const float4 &p, float w, bool vec) {
+    if (vec) {
+        float4 e = *reinterpret_cast<const float4 *>(sh);
+        e.x = ema_follow(e.x, p.x, w); e.y = ema_follow(e.y, p.y, w);
+        e.z = ema_follow(e.z, p.z, w); e.w = ema_follow(e.w, p.w, w);
+        *reinterpret_cast<float4 *>(sh) = e;
+        return;
+    }
+    const float e0 = sh[0], e1 = sh[1], e2 = sh[2], e3 = sh[3];
+    sh[0] = ema_follow(e0, p.x, w); sh[1] = ema_follow(e1, p.y, w);
+    sh[2] = ema_follow(e2, p.z, w); sh[3] = ema_follow(e3, p.w, w);
+}
+
+// The shadow behind the SCALAR loop of a step (tensors that are short, ragged or misaligned): a second sweep in which every
+// thread revisits the elements it has just written.  The scalar loop itself stays free of the shadow so that it compiles to
+// the instructions it has in the plain step -- with the shadow's arithmetic in its block the compiler contracts `upd`
+// differently, and p would no longer come out bit for bit as without averaging.
+__device__ __forceinline__ void ema_follow_scalar(float *sh, const float *p, long long lo, long long hi, float w) {
+    for (long long i = lo + threadIdx.x; i < hi; i += 256) sh[i] = ema_follow(sh[i], p[i], w);
+}
+
 // SCALED = false is the body of lvt_adam_step as it always was (gscale and clamp are dead); SCALED = true: lvt_adam_step_scaled.
-template <bool SCALED>
+// EMA = true (lvt_adam_step_ema): the shadow ema[t] of every tensor follows the new parameter value while it is still in a
+// register; EMA = false leaves `ema` and `w` dead, and the two instantiations without it are what they were.
+template <bool SCALED, bool EMA>
 __device__ __forceinline__ void adam_body(const OptArgs &a, float beta1, float beta2, float eps, float bc1, float bc2_sqrt,
-                                          const lvt_clip_record *gscale, float clamp) {
+                                          const lvt_clip_record *gscale, float clamp, float *const *ema, float w) {
     float coef = 1.f;
     if (SCALED && gscale) {
         if (gscale->skip) return;           // non-finite gradient norm: no store, p / s0 / s1 keep their bits
@@ -62,6 +100,8 @@ __device__ __forceinline__ void adam_body(const OptArgs &a, float beta1, float b
         const float denom = sqrtf(v) / bc2_sqrt + eps;
         return p - step * (m / denom);
     };
+    float *const sh = EMA ? ema[t] : nullptr;
+    const bool sh_vec = EMA && ((uintptr_t)sh & 15) == 0;
     if (opt_vec_ok(e, lo)) {                // 16-byte lanes: a wave instruction moves 1 KB instead of 256 B
         for (long long i = lo + 4 * threadIdx.x; i < hi; i += 1024) {
             const float4 g4 = *reinterpret_cast<const float4 *>(e.g + i), p4 = *reinterpret_cast<const float4 *>(e.p + i);
@@ -70,30 +110,40 @@ __device__ __forceinline__ void adam_body(const OptArgs &a, float beta1, float b
             o.z = upd(g4.z, p4.z, m4.z, v4.z); o.w = upd(g4.w, p4.w, m4.w, v4.w);
             *reinterpret_cast<float4 *>(e.s0 + i) = m4; *reinterpret_cast<float4 *>(e.s1 + i) = v4;
             *reinterpret_cast<float4 *>(e.p + i) = o;
+            if (EMA) ema_follow4(sh + i, o, w, sh_vec);
         }
         return;
     }
     for (long long i = lo + threadIdx.x; i < hi; i += 256) {
         float m = e.s0[i], v = e.s1[i];
-        e.p[i] = upd(e.g[i], e.p[i], m, v);
+        const float o = upd(e.g[i], e.p[i], m, v);
+        e.p[i] = o;
         e.s0[i] = m; e.s1[i] = v;
     }
+    if (EMA) ema_follow_scalar(sh, e.p, lo, hi, w);
 }
 
 __global__ __launch_bounds__(256) void lvt_adam_kernel(const OptArgs a, float beta1, float beta2, float eps,
                                                        float bc1, float bc2_sqrt) {
-    adam_body<false>(a, beta1, beta2, eps, bc1, bc2_sqrt, nullptr, 0.f);
+    adam_body<false, false>(a, beta1, beta2, eps, bc1, bc2_sqrt, nullptr, 0.f, nullptr, 0.f);
 }
 
 __global__ __launch_bounds__(256) void lvt_adam_scaled_kernel(const OptArgs a, float beta1, float beta2, float eps,
                                                               float bc1, float bc2_sqrt, const lvt_clip_record *gscale,
                                                               float clamp) {
-    adam_body<true>(a, beta1, beta2, eps, bc1, bc2_sqrt, gscale, clamp);
+    adam_body<true, false>(a, beta1, beta2, eps, bc1, bc2_sqrt, gscale, clamp, nullptr, 0.f);
 }
 
+// The EMA variants carry the table and the shadows in one by-value struct.  gscale == NULL and clamp == 0 launch the unscaled body.
 template <bool SCALED>
+__global__ __launch_bounds__(256) void lvt_adam_ema_kernel(const EmaArgs a, float beta1, float beta2, float eps, float bc1,
+                                                           float bc2_sqrt, const lvt_clip_record *gscale, float clamp, float w) {
+    adam_body<SCALED, true>(a.a, beta1, beta2, eps, bc1, bc2_sqrt, gscale, clamp, a.ema, w);
+}
+
+template <bool SCALED, bool EMA>
 __device__ __forceinline__ void rmsprop_body(const OptArgs &a, float alpha, float eps, float momentum,
-                                             const lvt_clip_record *gscale, float clamp) {
+                                             const lvt_clip_record *gscale, float clamp, float *const *ema, float w) {
     float coef = 1.f;
     if (SCALED && gscale) {
         if (gscale->skip) return;
@@ -112,6 +162,8 @@ __device__ __forceinline__ void rmsprop_body(const OptArgs &a, float alpha, floa
         return p - e.lr * (g / avg);
     };
     const bool mom = momentum > 0.f;
+    float *const sh = EMA ? ema[t] : nullptr;
+    const bool sh_vec = EMA && ((uintptr_t)sh & 15) == 0;
     if (opt_vec_ok(e, lo)) {
         for (long long i = lo + 4 * threadIdx.x; i < hi; i += 1024) {
             const float4 g4 = *reinterpret_cast<const float4 *>(e.g + i), p4 = *reinterpret_cast<const float4 *>(e.p + i);
@@ -122,24 +174,54 @@ __device__ __forceinline__ void rmsprop_body(const OptArgs &a, float alpha, floa
             *reinterpret_cast<float4 *>(e.s0 + i) = s4;
             if (mom) *reinterpret_cast<float4 *>(e.s1 + i) = b4;
             *reinterpret_cast<float4 *>(e.p + i) = o;
+            if (EMA) ema_follow4(sh + i, o, w, sh_vec);
         }
         return;
     }
     for (long long i = lo + threadIdx.x; i < hi; i += 256) {
         float sq = e.s0[i], buf = mom ? e.s1[i] : 0.f;
-        e.p[i] = upd(e.g[i], e.p[i], sq, buf);
+        const float o = upd(e.g[i], e.p[i], sq, buf);
+        e.p[i] = o;
         e.s0[i] = sq;
         if (mom) e.s1[i] = buf;
     }
+    if (EMA) ema_follow_scalar(sh, e.p, lo, hi, w);
 }
 
 __global__ __launch_bounds__(256) void lvt_rmsprop_kernel(const OptArgs a, float alpha, float eps, float momentum) {
-    rmsprop_body<false>(a, alpha, eps, momentum, nullptr, 0.f);
+    rmsprop_body<false, false>(a, alpha, eps, momentum, nullptr, 0.f, nullptr, 0.f);
 }
 
 __global__ __launch_bounds__(256) void lvt_rmsprop_scaled_kernel(const OptArgs a, float alpha, float eps, float momentum,
                                                                  const lvt_clip_record *gscale, float clamp) {
-    rmsprop_body<true>(a, alpha, eps, momentum, gscale, clamp);
+    rmsprop_body<true, false>(a, alpha, eps, momentum, gscale, clamp, nullptr, 0.f);
+}
+
+template <bool SCALED>
+__global__ __launch_bounds__(256) void lvt_rmsprop_ema_kernel(const EmaArgs a, float alpha, float eps, float momentum,
+                                                              const lvt_clip_record *gscale, float clamp, float w) {
+    rmsprop_body<SCALED, true>(a.a, alpha, eps, momentum, gscale, clamp, a.ema, w);
+}
+
+// Exchange of the contents of e.p and e.s0 (lvt_ema_swap): the chunking of the steps, float4 lanes when both sides allow.
+__global__ __launch_bounds__(256) void lvt_ema_swap_kernel(const OptArgs a) {
+    const int t = find_tensor(a, blockIdx.x);
+    const LvtOptEntry e = a.e[t];
+    const long long lo = (long long)(blockIdx.x - a.chunk_prefix[t]) * OPT_CHUNK;
+    const long long hi = min(e.n, lo + OPT_CHUNK);
+    if ((((uintptr_t)e.p | (uintptr_t)e.s0) & 15) == 0 && (e.n & 3) == 0) {
+        for (long long i = lo + 4 * threadIdx.x; i < hi; i += 1024) {
+            const float4 x = *reinterpret_cast<const float4 *>(e.p + i), y = *reinterpret_cast<const float4 *>(e.s0 + i);
+            *reinterpret_cast<float4 *>(e.p + i) = y;
+            *reinterpret_cast<float4 *>(e.s0 + i) = x;
+        }
+        return;
+    }
+    for (long long i = lo + threadIdx.x; i < hi; i += 256) {
+        const float x = e.p[i], y = e.s0[i];
+        e.p[i] = y;
+        e.s0[i] = x;
+    }
 }
 
 // ---- global gradient norm (ABI 680) ------------------------------------------------------------------------------------------
@@ -261,6 +343,101 @@ extern "C" int lvt_rmsprop_step_scaled(const LvtOptEntry *host, int n, float alp
     return for_each_group(host, n, [&](const OptArgs &a, int blocks) {
         hipLaunchKernelGGL(lvt_rmsprop_scaled_kernel, dim3(blocks), dim3(256), 0, s, a, alpha, eps, momentum, gscale, clamp);
     });
+}
+
+// ---- Polyak-averaged weights inside the steps ---------------------------------------------------------------------------------
+template <typename Launch>
+static int for_each_group_ema(const LvtOptEntry *host, float *const *ema, int n, Launch launch) {
+    for (int base = 0; base < n; base += OPT_MAXT) {
+        EmaArgs a;
+        a.a.n = (n - base) < OPT_MAXT ? (n - base) : OPT_MAXT;
+        int blocks = 0;
+        for (int i = 0; i < a.a.n; ++i) {
+            a.a.e[i] = host[base + i];
+            a.ema[i] = ema[base + i];
+            if (!a.a.e[i].p || !a.a.e[i].g || !a.a.e[i].s0 || a.a.e[i].n <= 0) {
+                lvt_set_error("optimizer: bad entry %d", base + i);
+                return LVT_EINVAL;
+            }
+            if (!a.ema[i] || (((uintptr_t)a.ema[i]) & 3) || a.ema[i] == a.a.e[i].p) {
+                lvt_set_error("optimizer: bad shadow %d (null, misaligned, or the parameter itself)", base + i);
+                return LVT_EINVAL;
+            }
+            a.a.chunk_prefix[i] = blocks;
+            blocks += (int)lvt_cdiv(a.a.e[i].n, OPT_CHUNK);
+        }
+        for (int i = a.a.n; i < OPT_MAXT; ++i) a.ema[i] = nullptr;
+        a.a.chunk_prefix[a.a.n] = blocks;
+        launch(a, blocks);
+        LVT_CHECK_LAUNCH("optimizer kernel");
+    }
+    return LVT_OK;
+}
+
+#define REQUIRE_EMA_ARGS(name)                                                                                               \
+    LVT_REQUIRE(ema, name ": null shadow table");                                                                            \
+    LVT_REQUIRE(w >= 0.f && w <= 1.f, name ": w = 1 - decay must lie in [0, 1]");                                            \
+    LVT_REQUIRE(clamp >= 0.f && clamp < __builtin_inff() && (((uintptr_t)gscale) & 15) == 0,                                 \
+                name ": gscale must be 16-byte aligned and clamp finite and >= 0")
+
+extern "C" int lvt_adam_step_ema(const LvtOptEntry *host, float *const *ema, int n, float beta1, float beta2, float eps,
+                                 int step, float w, const lvt_clip_record *gscale, float clamp, void *stream) {
+    LVT_REQUIRE(host && n > 0 && step > 0, "adam_step_ema: bad args");
+    REQUIRE_EMA_ARGS("adam_step_ema");
+    hipStream_t s = (hipStream_t)stream;
+    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+    const bool scaled = gscale || clamp > 0.f;
+    return for_each_group_ema(host, ema, n, [&](const EmaArgs &a, int blocks) {
+        if (scaled)
+            hipLaunchKernelGGL(lvt_adam_ema_kernel<true>, dim3(blocks), dim3(256), 0, s, a, beta1, beta2, eps, (float)bc1,
+                               (float)sqrt(bc2), gscale, clamp, w);
+        else
+            hipLaunchKernelGGL(lvt_adam_ema_kernel<false>, dim3(blocks), dim3(256), 0, s, a, beta1, beta2, eps, (float)bc1,
+                               (float)sqrt(bc2), gscale, clamp, w);
+    });
+}
+
+extern "C" int lvt_rmsprop_step_ema(const LvtOptEntry *host, float *const *ema, int n, float alpha, float eps, float momentum,
+                                    float w, const lvt_clip_record *gscale, float clamp, void *stream) {
+    LVT_REQUIRE(host && n > 0, "rmsprop_step_ema: bad args");
+    REQUIRE_EMA_ARGS("rmsprop_step_ema");
+    hipStream_t s = (hipStream_t)stream;
+    const bool scaled = gscale || clamp > 0.f;
+    return for_each_group_ema(host, ema, n, [&](const EmaArgs &a, int blocks) {
+        if (scaled)
+            hipLaunchKernelGGL(lvt_rmsprop_ema_kernel<true>, dim3(blocks), dim3(256), 0, s, a, alpha, eps, momentum, gscale,
+                               clamp, w);
+        else
+            hipLaunchKernelGGL(lvt_rmsprop_ema_kernel<false>, dim3(blocks), dim3(256), 0, s, a, alpha, eps, momentum, gscale,
+                               clamp, w);
+    });
+}
+
+extern "C" int lvt_ema_swap(float *const *pa, float *const *pb, const long long *counts, int n, void *stream) {
+    LVT_REQUIRE(pa && pb && counts && n > 0, "ema_swap: bad args");
+    hipStream_t s = (hipStream_t)stream;
+    for (int base = 0; base < n; base += OPT_MAXT) {
+        OptArgs a = {};
+        a.n = (n - base) < OPT_MAXT ? (n - base) : OPT_MAXT;
+        long long blocks = 0;
+        for (int i = 0; i < a.n; ++i) {
+            float *x = pa[base + i], *y = pb[base + i];
+            const long long cnt = counts[base + i];
+            LVT_REQUIRE(x && y && x != y && cnt > 0 && ((((uintptr_t)x) | ((uintptr_t)y)) & 3) == 0,
+                        "ema_swap: bad entry %d (null, misaligned or identical pointers, or no elements)", base + i);
+            LVT_REQUIRE((x + cnt <= y) || (y + cnt <= x), "ema_swap: entry %d overlaps itself", base + i);
+            a.e[i].p = x;
+            a.e[i].s0 = y;
+            a.e[i].n = cnt;
+            a.chunk_prefix[i] = (int)blocks;
+            blocks += lvt_cdiv(cnt, OPT_CHUNK);
+        }
+        LVT_REQUIRE(blocks < (1ll << 31), "ema_swap: too many chunks in one launch");
+        a.chunk_prefix[a.n] = (int)blocks;
+        hipLaunchKernelGGL(lvt_ema_swap_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
+        LVT_CHECK_LAUNCH("ema_swap kernel");
+    }
+    return LVT_OK;
 }
 
 extern "C" long long lvt_grad_sqnorm_partials(const lvt_grad_entry *host, int n) {

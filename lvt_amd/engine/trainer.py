@@ -12,14 +12,21 @@ train_loop.py:112-133, defaults.py:273-310), minus its per-step host synchronisa
     Disabled (the default), the trainer holds no clipper and the sequence above is unchanged.
   * MODEL.CODEBOOK.RESTART: `codebook_perplexity`, `codebook_dead` and `codebook_restarts` (device scalars of the quantiser's
     health record) ride in the same copy.  Off (the default), nothing changes.
+  * SOLVER.MODEL_EMA (solver/ema.py): the fused optimizers keep a Polyak average of every parameter they step, inside the step
+    launch, so it advances exactly on the iterations that step (ACCUMULATION_STEPS is respected) and costs no host
+    synchronisation.  Every checkpoint gets an averaged twin `model_*_ema.pth` with the module's own keys (sub-networks with an
+    optimizer only); `last_checkpoint` keeps naming the live file.  Resuming restores the shadows from the twin of the resumed
+    file, or starts them from the loaded weights.  Off (the default), the trainer holds no ModelEma and nothing changes.
   * checkpoints: one Checkpointer per sub-network, `model_{iter:07d}.pth` / `model_final.pth`, rank 0 only.
 """
 import logging
+import os
 import time
 
 import torch
 
-from ..solver.build import build_grad_clipper
+from ..solver.build import build_grad_clipper, build_model_ema
+from ..solver.ema import ema_twin
 from ..utils import comm
 from ..utils.checkpoint import PeriodicCheckpointer
 from ..utils.events import EventStorage
@@ -32,6 +39,7 @@ class Trainer:
         if comm.get_world_size() > 1:
             model.wrap_parallel(device_ids=[comm.get_local_rank()], broadcast_buffers=False)
         self.clipper = build_grad_clipper(cfg, self.optimizers)       # None unless SOLVER.CLIP_GRADIENTS.ENABLED
+        self.model_ema = build_model_ema(cfg, self.optimizers)        # None unless SOLVER.MODEL_EMA.ENABLED
         model.train()
         self.start_iter, self.max_iter = 0, cfg.SOLVER.MAX_ITER
         self.accumulation_steps = cfg.SOLVER.ACCUMULATION_STEPS
@@ -42,7 +50,28 @@ class Trainer:
 
     def resume_or_load(self, resume=True):
         for item in self.checkpointers:
-            item["checkpointer"].resume_or_load(item["pretrained"], resume=resume)
+            ck = item["checkpointer"]
+            resumed = ck.get_checkpoint_file() if resume and ck.has_checkpoint() else ""
+            ck.resume_or_load(item["pretrained"], resume=resume)
+            if self.model_ema is None or not self.model_ema.owns(ck.model):
+                continue
+            twin = ema_twin(resumed) if resumed else ""
+            if twin and os.path.isfile(twin):           # the averaged weights that went with the resumed checkpoint
+                data = torch.load(twin, map_location="cpu")
+                self.model_ema.load_shadows(ck.model, data["model"], data.get("ema_updates"))
+                self.logger.info("averaged weights of %s restored from %s", os.path.basename(ck.save_dir), twin)
+            else:                                       # none on disk: the average restarts from the loaded weights
+                self.model_ema.reset_shadows(ck.model)
+
+    def _save_twins(self):
+        """`model_*_ema.pth` next to every checkpoint written at this iteration: the state dict of each sub-network that has
+        an optimizer, taken while the parameters hold the averaged weights (buffers are the live ones)."""
+        if self.model_ema is None or not self.periodic or not self.periodic[0].due(self.iter):
+            return
+        with self.model_ema.averaged():
+            for pc in self.periodic:
+                if self.model_ema.owns(pc.checkpointer.model):
+                    pc.step_twin(self.iter, ema_updates=self.model_ema.updates)
 
     def run_step(self):
         assert self.model.training, "model was changed to eval mode!"
@@ -97,5 +126,6 @@ class Trainer:
                                          "  ".join("%s: %.5f" % kv for kv in vals.items()), dt)
                 for pc in self.periodic:
                     pc.step(self.iter)
+                self._save_twins()
                 storage.step()
         return last

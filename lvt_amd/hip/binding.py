@@ -223,6 +223,9 @@ def _declare(lib):
         "lvt_rmsprop_step": (ci, [P(OptEntry), ci, cf, cf, cf, vp]),
         "lvt_adam_step_scaled": (ci, [P(OptEntry), ci, cf, cf, cf, ci, vp, cf, vp]),
         "lvt_rmsprop_step_scaled": (ci, [P(OptEntry), ci, cf, cf, cf, vp, cf, vp]),
+        "lvt_adam_step_ema": (ci, [P(OptEntry), P(vp), ci, cf, cf, cf, ci, cf, vp, cf, vp]),
+        "lvt_rmsprop_step_ema": (ci, [P(OptEntry), P(vp), ci, cf, cf, cf, cf, vp, cf, vp]),
+        "lvt_ema_swap": (ci, [P(vp), P(vp), P(cll), ci, vp]),
         "lvt_grad_sqnorm_partials": (cll, [P(GradEntry), ci]),
         "lvt_grad_sqnorm": (ci, [P(GradEntry), ci, vp, cll, vp]),
         "lvt_grad_clip_coef": (ci, [vp, cll, cf, vp, vp, vp]),

@@ -9,7 +9,8 @@ import torch
 from torch.optim.lr_scheduler import LambdaLR
 
 from .clip import GradClipper, check_clip_args
-from .fused import FusedAdam, FusedRMSprop
+from .ema import ModelEma
+from .fused import FusedAdam, FusedRMSprop, check_ema_decay
 
 _NORM_TYPES = (torch.nn.BatchNorm1d, torch.nn.BatchNorm2d, torch.nn.BatchNorm3d, torch.nn.SyncBatchNorm,
                torch.nn.GroupNorm, torch.nn.InstanceNorm1d, torch.nn.InstanceNorm2d, torch.nn.InstanceNorm3d,
@@ -56,6 +57,16 @@ def build_grad_clipper(cfg, optimizers):
         return None
     return GradClipper([o["optimizer"] if isinstance(o, dict) else o for o in optimizers], c.CLIP_TYPE, c.CLIP_VALUE,
                        c.NORM_TYPE)
+
+
+def build_model_ema(cfg, optimizers):
+    """SOLVER.MODEL_EMA -> a ModelEma over ALL the given optimizers (the objects, or the {"optimizer": ...} items the
+    meta-architectures return), or None when disabled.  A bad DECAY is a ValueError whether or not averaging is enabled."""
+    c = cfg.SOLVER.MODEL_EMA
+    check_ema_decay(c.DECAY)
+    if not c.ENABLED:
+        return None
+    return ModelEma(optimizers, c.DECAY, c.WARMUP)
 
 
 def _warmup_factor(method, it, warmup_iters, warmup_factor):

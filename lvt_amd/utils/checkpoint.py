@@ -16,16 +16,21 @@ class Checkpointer:
         self.save_to_disk = save_to_disk
         self.checkpointables = dict(checkpointables)
 
-    def save(self, name, **kwargs):
+    def save(self, name, twin=False, **kwargs):
+        """`twin=True` writes a file that goes WITH a checkpoint (the averaged weights of solver/ema.py): the model's state dict
+        and `kwargs` only, and `last_checkpoint` keeps naming the checkpoint itself."""
         if not self.save_dir or not self.save_to_disk:
             return
         data = {"model": self.model.state_dict()}
-        for k, obj in self.checkpointables.items():
-            data[k] = obj.state_dict()
+        if not twin:
+            for k, obj in self.checkpointables.items():
+                data[k] = obj.state_dict()
         data.update(kwargs)
         os.makedirs(self.save_dir, exist_ok=True)
         basename = "{}.pth".format(name)
         torch.save(data, os.path.join(self.save_dir, basename))
+        if twin:
+            return
         with open(os.path.join(self.save_dir, "last_checkpoint"), "w") as f:
             f.write(basename)
 
@@ -70,9 +75,21 @@ class PeriodicCheckpointer:
     def __init__(self, checkpointer, period, max_iter=None):
         self.checkpointer, self.period, self.max_iter = checkpointer, int(period), max_iter
 
-    def step(self, iteration, **kwargs):
-        iteration = int(iteration)
+    def due(self, iteration):
+        """Names of the checkpoints `step(iteration)` writes."""
+        iteration, names = int(iteration), []
         if (iteration + 1) % self.period == 0:
-            self.checkpointer.save("model_{:07d}".format(iteration), iteration=iteration, **kwargs)
+            names.append("model_{:07d}".format(iteration))
         if self.max_iter is not None and iteration >= self.max_iter - 1:
-            self.checkpointer.save("model_final", iteration=iteration, **kwargs)
+            names.append("model_final")
+        return names
+
+    def step(self, iteration, **kwargs):
+        for name in self.due(iteration):
+            self.checkpointer.save(name, iteration=int(iteration), **kwargs)
+
+    def step_twin(self, iteration, suffix="_ema", **kwargs):
+        """`<name><suffix>.pth` next to every checkpoint `step(iteration)` writes, from the model as it is NOW (the caller
+        holds it in the state the twin records); the `last_checkpoint` marker is left alone."""
+        for name in self.due(iteration):
+            self.checkpointer.save(name + suffix, twin=True, iteration=int(iteration), **kwargs)

@@ -29,6 +29,7 @@ from lvt_amd.data.samplers import TrainingSampler  # noqa: E402
 from lvt_amd.engine.trainer import Trainer  # noqa: E402
 from lvt_amd.evaluation import build_evaluator, inference_on_dataset  # noqa: E402
 from lvt_amd.modeling import build_model  # noqa: E402
+from lvt_amd.solver.ema import ema_twin  # noqa: E402
 from lvt_amd.utils import comm  # noqa: E402
 
 
@@ -161,7 +162,11 @@ def main(args):
         # the model in inference mode and hand (inputs, outputs) to the evaluators cfg.TEST.EVALUATORS names
         _, checkpointers = model.configure_optimizers_and_checkpointers()
         for item in checkpointers:
-            item["checkpointer"].resume_or_load(item["pretrained"], resume=False)
+            path = item["pretrained"]
+            if cfg.SOLVER.MODEL_EMA.ENABLED and path and os.path.isfile(ema_twin(path)):
+                path = ema_twin(path)        # the averaged weights written next to the checkpoint (module's own keys)
+                logging.getLogger("lvt_amd").info("loading averaged weights %s", path)
+            item["checkpointer"].resume_or_load(path, resume=False)
         evaluator = build_evaluator(cfg, cfg.DATASETS.TEST[0] if len(cfg.DATASETS.TEST) else "test")
         res = inference_on_dataset(model, test_batches(cfg, args), evaluator)
         if comm.is_main_process():
