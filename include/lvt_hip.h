@@ -756,6 +756,28 @@ int lvt_upsample2x2(const float *x, int N, int H, int W, int Cp, float scale, co
 int lvt_pixel_shuffle2(const float *x, int N, int H, int W, int C, int act, float *out, float *out_amax, void *stream);
 int lvt_pixel_unshuffle2(const float *g, int N, int H, int W, int C, float *out, float *out_amax, void *stream);
 
+/* ---- per-frame PSNR and SSIM (additive under ABI 680; csrc/quality.hip; the rule in plain Python: lvt_amd/evaluation/quality.py).
+ * a, b: fp32 frames (F, C, H, W), channels-first and contiguous, any H, W >= 11.  SSIM after Wang et al. 2004: 11x11 Gaussian
+ * window of sigma 1.5 normalised to sum 1, no padding (the map of a plane is (H-10) x (W-10)), weighted biased variances and
+ * covariance, C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2; the SSIM of a frame is the mean of the map over its channels
+ * and positions.  PSNR of a frame: 10 log10(data_range^2 / mse), mse over all its channels.  Two launches on one stream:
+ *   1. lvt_frame_quality: one workgroup per (plane, 16 x 32 tile of the map); the windowed second moments are taken about a
+ *      per-tile pivot in fp32, the ratio in fp64.  partials[(f * n_partials + i) * 2 + {0, 1}] = {sum of the SSIM map over tile i
+ *      of frame f, sum of (a - b)^2 over the input pixels tile i owns} in fp64 (every pixel belongs to exactly one tile), plain
+ *      stores.  partials: F * n_partials * 2 doubles, 16-byte aligned.
+ *   2. lvt_frame_quality_finish: one workgroup adds each frame's partials in a fixed order: frames[2 f] = psnr (+inf for a frame
+ *      with mse == 0), frames[2 f + 1] = ssim; then acc[0] += sum of the psnr of the frames with mse != 0, acc[1] += sum of ssim,
+ *      acc[2] += number of frames with mse != 0, acc[3] += F.  acc: 4 doubles the caller owns and zeroes; this launch is its
+ *      only writer.
+ * n_partials must equal lvt_frame_quality_partials (host arithmetic: tiles per frame, C * ceil((H-10) / 16) * ceil((W-10) / 32);
+ * -1 for C <= 0 or H or W below 11).  A null or misaligned pointer, F or C <= 0, H or W below 11, a data_range that is not
+ * positive and finite, another n_partials: LVT_EINVAL before any device work.  No atomics: the same inputs give the same bits. */
+long long lvt_frame_quality_partials(int C, int H, int W);
+int lvt_frame_quality(const float *a, const float *b, int F, int C, int H, int W, double data_range, double *partials,
+                      long long n_partials, void *stream);
+int lvt_frame_quality_finish(const double *partials, int F, int C, int H, int W, double data_range, long long n_partials,
+                             double *frames, double *acc, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

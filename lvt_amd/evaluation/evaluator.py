@@ -15,6 +15,7 @@ import torch.nn.functional as F
 from ..data.latents import save_video_codes
 from ..layers import all_reduce_sum_
 from ..utils import comm
+from .quality import frame_quality_reference
 
 
 class DatasetEvaluator:
@@ -111,6 +112,57 @@ class MSEEvaluator(_SumEvaluator):
         if not comm.is_main_process():
             return None
         results = OrderedDict({"reconstruction": {"MSE": s / n}})
+        self._logger.info(results)
+        return results
+
+
+class FrameQualityEvaluator(DatasetEvaluator):
+    """Mean per-frame PSNR and SSIM of `out["reconstruction"]` against the input frames, the unit reconstructions are compared
+    in (definitions: evaluation/quality.py).  Device tensors go through `ew.frame_quality` (csrc/quality.hip) into one device
+    accumulator [sum psnr, sum ssim, frames with a finite psnr, frames]; CPU tensors through `frame_quality_reference` into the
+    same four sums.  A frame that is reproduced exactly (mse == 0) has no finite PSNR: it is left out of the PSNR mean and
+    counted as `identical_frames`; its SSIM of 1 counts."""
+
+    def __init__(self, dataset_name, distributed=True, output_dir=None, data_range=1.0):
+        self._logger = logging.getLogger(__name__)
+        self._distributed = distributed
+        self._data_range = float(data_range)
+        if not (self._data_range > 0 and math.isfinite(self._data_range)):
+            raise ValueError("FrameQualityEvaluator: data_range must be positive and finite, got %r" % (data_range,))
+        self.reset()
+
+    def reset(self):
+        self._acc = None                      # the four sums on the device of the first output
+
+    def process(self, inputs, outputs):
+        for inp, out in zip(inputs, outputs):
+            rec = out["reconstruction"].detach()
+            tgt = torch.as_tensor(inp["image"] if "image" in inp else inp["image_sequence"], device=rec.device)
+            if self._acc is None:
+                self._acc = torch.zeros(4, dtype=torch.float64, device=rec.device)
+            if rec.is_cuda:
+                from ..hip import ew
+                ew.frame_quality(rec.contiguous().float(), tgt.to(torch.float32).contiguous(), self._data_range, acc=self._acc)
+            else:
+                psnr, ssim = frame_quality_reference(rec, tgt, self._data_range)
+                finite = psnr != float("inf")                    # (mse != 0, as the kernel counts)
+                self._acc += torch.stack([psnr[finite].sum(), ssim.sum(), finite.sum().double(),
+                                          torch.tensor(float(psnr.numel()), dtype=torch.float64)])
+
+    def evaluate(self):
+        if self._acc is None:                 # a rank that saw no sample still takes part in the all-reduce
+            dist_on = self._distributed and torch.distributed.is_available() and torch.distributed.is_initialized()
+            dev = "cuda" if (dist_on and torch.cuda.is_available() and torch.distributed.get_backend() == "nccl") else "cpu"
+            self._acc = torch.zeros(4, dtype=torch.float64, device=dev)
+        acc = self._acc.clone()
+        if self._distributed:
+            all_reduce_sum_(acc)
+        if not comm.is_main_process():
+            return None
+        psnr_sum, ssim_sum, finite, n = (float(v) for v in acc.cpu())
+        results = OrderedDict({"frame_quality": {"PSNR": psnr_sum / finite if finite > 0 else float("nan"),
+                                                 "SSIM": ssim_sum / n if n > 0 else float("nan"),
+                                                 "frames": int(n), "identical_frames": int(n - finite)}})
         self._logger.info(results)
         return results
 
@@ -215,6 +267,9 @@ def build_evaluator(cfg, dataset_name, output_folder=None):
         evs.append(CodesExtractor(dataset_name, True, output_folder))
     if "MSEEvaluator" in cfg.TEST.EVALUATORS:
         evs.append(MSEEvaluator(dataset_name, True, output_folder))
+    if "FrameQualityEvaluator" in cfg.TEST.EVALUATORS:    # the range AutoEncoderModel's inference clamps its reconstructions to
+        evs.append(FrameQualityEvaluator(dataset_name, True, output_folder,
+                                         data_range=1.0 if cfg.INPUT.SCALE_TO_ZEROONE else 255.0))
     if "BitsEvaluator" in cfg.TEST.EVALUATORS:
         evs.append(BitsEvaluator(dataset_name, True, output_folder))
     if "VTSampler" in cfg.TEST.EVALUATORS:

@@ -1,0 +1,68 @@
+"""Per-frame PSNR and SSIM, stated once in plain torch (any device, any float dtype).  `frame_quality_reference` is the CPU branch
+of `FrameQualityEvaluator` and the rule the gfx950 kernel behind `lvt_amd.hip.ew.frame_quality` is tested against
+(csrc/quality.hip).
+
+SSIM follows Wang, Bovik, Sheikh, Simoncelli, "Image quality assessment: from error visibility to structural similarity" (IEEE
+TIP 2004): an 11x11 Gaussian window of sigma 1.5 normalised to sum 1 and applied separably, no padding (the map of an H x W plane
+is (H-10) x (W-10)), the weighted biased variances and covariance E_w[xy] - mu_x mu_y, C1 = (0.01 L)^2, C2 = (0.03 L)^2 with L
+the data range; the SSIM of a frame is the mean of the map over all its channels and positions.  This is the definition of
+`skimage.metrics.structural_similarity(gaussian_weights=True, use_sample_covariance=False)` and the default of `pytorch_msssim`
+(neither is a dependency of this package, and neither was at hand to compare with).
+
+PSNR of a frame is 10 log10(L^2 / mse) with the mse over all channels of the frame; a frame with mse == 0 has none (+inf)."""
+import math
+
+import torch
+
+WINDOW, SIGMA = 11, 1.5
+
+
+def gaussian_window(dtype=torch.float64, device=None):
+    """The 11 taps exp(-(k - 5)^2 / (2 sigma^2)) normalised to sum 1 (formed in fp64, then cast)."""
+    k = torch.arange(WINDOW, dtype=torch.float64) - (WINDOW - 1) / 2
+    g = torch.exp(-k * k / (2 * SIGMA * SIGMA))
+    return (g / g.sum()).to(dtype=dtype, device=device)
+
+
+def windowed(x, win):
+    """Separable valid correlation of the last two axes of `x` with the 1-D window: (..., H, W) -> (..., H-10, W-10)."""
+    n = win.numel()
+    W = x.shape[-1] - n + 1
+    h = sum(win[k] * x[..., :, k:k + W] for k in range(n))
+    H = x.shape[-2] - n + 1
+    return sum(win[k] * h[..., k:k + H, :] for k in range(n))
+
+
+def check_frames(a, b, data_range):
+    """The refusals shared by the reference and the device op: -> (a, b) as (F, C, H, W), or ValueError naming the cause."""
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError("frame quality: shapes differ, %s against %s" % (tuple(a.shape), tuple(b.shape)))
+    if a.dim() == 3:
+        a, b = a[None], b[None]
+    if a.dim() != 4:
+        raise ValueError("frame quality: frames are (F, C, H, W) or (C, H, W), got %s" % (tuple(a.shape),))
+    if a.shape[-2] < WINDOW or a.shape[-1] < WINDOW:
+        raise ValueError("frame quality: H=%d W=%d, the 11x11 window needs H and W >= 11" % (a.shape[-2], a.shape[-1]))
+    if a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("frame quality: no frames or no channels in %s" % (tuple(a.shape),))
+    data_range = float(data_range)
+    if not (data_range > 0 and math.isfinite(data_range)):
+        raise ValueError("frame quality: data_range must be positive and finite, got %r" % (data_range,))
+    return a, b
+
+
+def frame_quality_reference(a, b, data_range, dtype=torch.float64):
+    """(F, C, H, W) frames a, b -> (psnr[F], ssim[F]) in `dtype`; psnr is +inf for a frame with mse == 0."""
+    a, b = check_frames(a, b, data_range)
+    x, y = a.to(dtype), b.to(dtype)
+    L = float(data_range)
+    mse = ((x - y) ** 2).mean(dim=(1, 2, 3))
+    psnr = torch.where(mse == 0, torch.full_like(mse, float("inf")), 10 * torch.log10(L * L / mse))
+    win = gaussian_window(dtype, x.device)
+    c1, c2 = (0.01 * L) ** 2, (0.03 * L) ** 2
+    mx, my = windowed(x, win), windowed(y, win)
+    sxx = windowed(x * x, win) - mx * mx
+    syy = windowed(y * y, win) - my * my
+    sxy = windowed(x * y, win) - mx * my
+    ssim = ((2 * (mx * my) + c1) * (2 * sxy + c2)) / ((mx * mx + my * my + c1) * (sxx + syy + c2))
+    return psnr, ssim.mean(dim=(1, 2, 3))

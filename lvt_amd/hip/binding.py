@@ -240,6 +240,9 @@ def _declare(lib):
         "lvt_upsample2x2": (ci, [vp, ci, ci, ci, ci, cf, vp, ci, vp, vp, vp]),
         "lvt_pixel_shuffle2": (ci, [vp, ci, ci, ci, ci, ci, vp, vp, vp]),
         "lvt_pixel_unshuffle2": (ci, [vp, ci, ci, ci, ci, vp, vp, vp]),
+        "lvt_frame_quality_partials": (cll, [ci, ci, ci]),
+        "lvt_frame_quality": (ci, [vp, vp, ci, ci, ci, ci, C.c_double, vp, cll, vp]),
+        "lvt_frame_quality_finish": (ci, [vp, ci, ci, ci, ci, C.c_double, cll, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)

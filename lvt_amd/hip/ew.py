@@ -44,6 +44,42 @@ def mse_fwd(a, b, denom, scale=1.0, l1=False):
     return out.view(())
 
 
+def frame_quality(a, b, data_range, acc=None, frames=None):
+    """Per-frame PSNR and SSIM of (F, C, H, W) or (C, H, W) fp32 device frames (csrc/quality.hip; the rule:
+    lvt_amd.evaluation.quality.frame_quality_reference) -> (frames, acc): frames (F, 2) float64 = [psnr, ssim] per frame, psnr
+    +inf where the frame's mse is 0; acc (4,) float64 += [sum of the finite psnr, sum of ssim, frames with a finite psnr, frames]
+    (a fresh zeroed one when none is passed).  `frames`: an (F, 2) float64 tensor to write into instead of a new one.  Nothing is
+    read on the host, and a refused call launches nothing."""
+    L.require(a, b, acc, frames)
+    if tuple(a.shape) != tuple(b.shape):
+        raise L.LvtError("frame_quality: shapes differ, %s against %s" % (tuple(a.shape), tuple(b.shape)))
+    if a.dim() not in (3, 4) or a.numel() == 0:
+        raise L.LvtError("frame_quality: frames are (F, C, H, W) or (C, H, W) and not empty, got %s" % (tuple(a.shape),))
+    if a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise L.LvtError("frame_quality: float32 frames only, got %s and %s" % (a.dtype, b.dtype))
+    F = a.shape[0] if a.dim() == 4 else 1
+    Cc, H, W = a.shape[-3:]
+    if H < 11 or W < 11:
+        raise L.LvtError("frame_quality: H=%d W=%d, the 11x11 window needs H and W >= 11" % (H, W))
+    data_range = float(data_range)
+    if not 0.0 < data_range < float("inf"):
+        raise L.LvtError("frame_quality: data_range must be positive and finite, got %r" % (data_range,))
+    if acc is None:
+        acc = torch.zeros(4, dtype=torch.float64, device=a.device)
+    elif acc.dtype != torch.float64 or acc.numel() != 4 or acc.device != a.device:
+        raise L.LvtError("frame_quality: acc is 4 float64 values on the frames' device")
+    n = L.lib().lvt_frame_quality_partials(Cc, H, W)
+    ws = L.workspace(F * n * 16, a.device, "frame_quality")
+    if frames is None:
+        frames = torch.empty(F, 2, dtype=torch.float64, device=a.device)
+    elif frames.dtype != torch.float64 or tuple(frames.shape) != (F, 2) or frames.device != a.device:
+        raise L.LvtError("frame_quality: frames is (%d, 2) float64 on the frames' device" % F)
+    L.check(L.lib().lvt_frame_quality(L.ptr(a), L.ptr(b), F, Cc, H, W, data_range, L.ptr(ws), n, L.stream_ptr()), "lvt_frame_quality")
+    L.check(L.lib().lvt_frame_quality_finish(L.ptr(ws), F, Cc, H, W, data_range, n, L.ptr(frames), L.ptr(acc), L.stream_ptr()),
+            "lvt_frame_quality_finish")
+    return frames, acc
+
+
 def mse_bwd(a, b, denom, scale=1.0, gout=None, add=None, tanh_of_a=False, l1=False):
     L.require(a, b, gout, add)
     out = torch.empty_like(a)
