@@ -250,11 +250,17 @@ struct FaSmem {
     float rs_inv[2][80];
     float dhs[32];                        // this head's dh bank (2 BH - 1 entries), in log2 units
 };
-template <int NR> struct FaSmemA {
-    unsigned short ring[2][FA_SLOT];
+// Kernel A runs at the register limit (256 with two waves per SIMD), so its layout and its body are written for the allocator:
+// the small arrays come FIRST -- a DS instruction reaches 64 KB from its address register, and behind the 72 KB ring every
+// rs_inv access needed an address register of its own, which the allocator spilled and reloaded in the key loop -- and what a
+// lane needs only after the loop waits in `keep` (one slot per lane, written and read by that lane alone).
+template <int NR, int ONEP> struct FaSmemA {
     float rs_inv[2][80];
     float dhs[32];
     float red[16];
+    float keep[ONEP ? 2 : 1][ONEP ? 512 : 4];   // one pass: [0] the lane's qinv, [1] its delta = dO . O, parked over the key loop
+                                          // (two passes: unused, 16 B)
+    unsigned short ring[2][FA_SLOT];
     float R[128 * 4 * NR];                // per-lane class sums of g (bias-bank gradient), [query][kg][NR]
 };
 struct FaSmem3 {                          // 256-thread workgroups: three-slot ring
@@ -270,6 +276,11 @@ __device__ __forceinline__ int fa_half(unsigned x) { return (int)((x >> 3) & 1);
 __device__ __forceinline__ int fa_pair4(unsigned x) { return (int)(((x >> 5) << 3) | (x & 7)); }
 __device__ __forceinline__ int fa_quarter(unsigned x) { return (int)((x >> 3) & 3); }
 __device__ __forceinline__ int fa_opaque(int x) { asm volatile("" : "+s"(x)); return x; }
+// x is formed HERE.  A running sum or maximum of the key loop is read only behind the loop; left alone, the compiler sinks the
+// whole chain of adds there and keeps every addend of every step live until then (kernel A, one pass: 48 spilled dwords per
+// lane, written step by step, and the registers they pushed out reloaded inside the loop).  The chain is evaluated in the
+// order written either way: no bit changes.
+__device__ __forceinline__ void fa_pin(float &x) { asm volatile("" : "+v"(x)); }
 
 template <int BH, int BW> struct Geo16 {
     static_assert(BW == 16 || BW == 8, "16-wide tiles: BW is 8 or 16");
@@ -474,7 +485,7 @@ __global__ __launch_bounds__(512, 1) void lvt_attn_fwd_flash_kernel(const FaArgs
 // returns dQ_i - eps_i C_i / temper, and hands kernel B delta + eps (B then forms g as the two-pass form did).
 // (The same prologue reordering in kernel B measured slower, 161.4 / 158.5 -> 164.5 / 160.7 us, and was not kept: DESIGN 3.5.)
 template <int BT, int BH, int BW, int MASKED, int NCH, int ONEP>
-__device__ __forceinline__ float fa_bwd_a_body(const FaArgs &A, FaSmemA<BT + Geo16<BH, BW>::HP + 4> &sm, int bh_, int qhalf) {
+__device__ __forceinline__ float fa_bwd_a_body(const FaArgs &A, FaSmemA<BT + Geo16<BH, BW>::HP + 4, ONEP> &sm, int bh_, int qhalf) {
     using GE = Geo16<BH, BW>;
     using BI = BankIdx<BT, BH, BW>;
     constexpr int HP = GE::HP;
@@ -532,6 +543,7 @@ __device__ __forceinline__ float fa_bwd_a_body(const FaArgs &A, FaSmemA<BT + Geo
     const float *dhl = sm.dhs + (hi + BH - 1 - (BW == 16 ? 0 : (kg >> 1)));
     constexpr int HSTEP = BW == 16 ? 1 : 2;
     const float qc = qinv * A.c1;
+    if constexpr (ONEP) { sm.keep[0][tid] = qinv; sm.keep[1][tid] = delta_early; }
     fa_park(g0, sm.ring[0], sm.rs_inv[0], tid);
     load_item(1, g0);
     __syncthreads();
@@ -541,7 +553,7 @@ __device__ __forceinline__ float fa_bwd_a_body(const FaArgs &A, FaSmemA<BT + Geo
     float sgf = 0.f, kmr = 0.f, dl = 0.f;                             // pass 2: scale of g from its bound, 1 / kmax (applied one
                                                                       // after the other: their product can leave the float range), delta / l
     int ebG = FA_EMIN;                                                // ONEP: the running exponent of max |g 2^(e_K - 14)| of this query row
-    if constexpr (ONEP) { delta = delta_early; dl = delta * linv; }
+    if constexpr (ONEP) dl = delta_early * linv;                      // (delta itself: sm.keep, read back behind the loop)
     f32x4v qacc[AT_D / 16];
 #pragma unroll
     for (int d = 0; d < AT_D / 16; ++d) qacc[d] = f32x4v{0.f, 0.f, 0.f, 0.f};
@@ -662,6 +674,15 @@ __device__ __forceinline__ float fa_bwd_a_body(const FaArgs &A, FaSmemA<BT + Geo
                 }
             }
             if constexpr (PASS2) { rst[T / HP] += gt; mine[BT + T % HP] += gt; }
+            // one pass: the loop-carried sums and the maximum take this tile's terms now (fa_pin), not behind the loop.  (The
+            // two-pass form is left as it compiles: with the pins the compiler contracts one of its class sums differently --
+            // the h bank gradient moved in the last bit, tests/test_gpu_flash_bwd_loop.py.)
+            if constexpr (ONEP) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) fa_pin(rsw[r]);
+                fa_pin(rst[T / HP]);
+                fa_pin(gmax);
+            }
             if constexpr (CORR) {
                 pku[2 * kt] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{pkv[0], pkv[1]}, f16x2v));
                 pku[2 * kt + 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{pkv[2], pkv[3]}, f16x2v));
@@ -712,7 +733,9 @@ __device__ __forceinline__ float fa_bwd_a_body(const FaArgs &A, FaSmemA<BT + Geo
     // (ONEP: acc = sum_j g 2^(e_K - 14) K~ 2^(141 - ebG), no common K scale)
     if constexpr (ONEP) {
         // per-workgroup bounds for kernel B: max 2^(e - 14) over the dO rows, max of max_j |g_ij| 2^(e_i - 14) over the q rows
-        float r0 = doinv, r1 = fa_kg_max(gmax) * qinv;
+        // (volatile: the lane's own slots, read here and not kept in registers over the loop)
+        float r0 = doinv, r1 = fa_kg_max(gmax) * *(volatile float *)&sm.keep[0][tid];
+        delta = *(volatile float *)&sm.keep[1][tid];
 #pragma unroll
         for (int dd = 32; dd > 0; dd >>= 1) { r0 = fmaxf(r0, __shfl_xor(r0, dd, 64)); r1 = fmaxf(r1, __shfl_xor(r1, dd, 64)); }
         if (lane == 0) { sm.red[wave] = r0; sm.red[8 + wave] = r1; }
@@ -737,6 +760,7 @@ __device__ __forceinline__ float fa_bwd_a_body(const FaArgs &A, FaSmemA<BT + Geo
             am = fmaxf(am, fmaxf(fmaxf(fabsf(ov[0]), fabsf(ov[1])), fmaxf(fabsf(ov[2]), fabsf(ov[3]))));
         }
     }
+    if constexpr (ONEP) fa_pin(am);    // (the masked launch runs a second body before it reads am: the max is taken here)
     if (kg == 0) A.delta[si] = delta;
     if (tid == 0) {
         float r0 = sm.red[0], r1 = sm.red[8];
@@ -793,7 +817,7 @@ __device__ __forceinline__ float fa_bwd_a_body(const FaArgs &A, FaSmemA<BT + Geo
 
 template <int BT, int BH, int BW, int MASKED, int ONEP>
 __global__ __launch_bounds__(512, 1) void lvt_attn_bwd_flash_a_kernel(const FaArgs A, float *__restrict__ d_amax) {
-    __shared__ __attribute__((aligned(16))) FaSmemA<BT + Geo16<BH, BW>::HP + 4> sm;
+    __shared__ __attribute__((aligned(16))) FaSmemA<BT + Geo16<BH, BW>::HP + 4, ONEP> sm;
     if (threadIdx.x >= 256) __builtin_amdgcn_s_setprio(1);           // (see the forward kernel)
     float am;
     if (MASKED) {        // one workgroup = both query halves of a (sample, head): 8 + 4 key chunks (as separate workgroups: 219 us against 182)
