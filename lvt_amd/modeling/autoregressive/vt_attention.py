@@ -194,8 +194,9 @@ FUSED_ATTENTION = True      # scores + bias + mask + softmax + P.V in one launch
 # backward (dQ, dK, dV, bank gradients) as three fused launches on 16-wide tiles (eight waves per workgroup, two per SIMD):
 # 147 + 184 + 151 us per layer at the DSFVT shape against 176 + ~410 us for the round-2 path (fused forward, four batched
 # GEMMs + softmax-bwd + bank kernel).  Used whenever the block has an instantiation ((1,16,16): DSFVT / KDSFVT; (4,8,8): DSSVT /
-# DSTSVT), 256 tokens x 128 head dims, bf16x3 arithmetic and batch x heads % 8 == 0.  LVT_NO_PLANE_ATTENTION=1 (or
-# PLANE_ATTENTION = False) keeps the round-2 path; tests force either side.
+# DSTSVT), 256 tokens x 128 head dims, batch x heads % 8 == 0 and the arithmetic is not f32: always in bf16x3, and in f16x2
+# when the flash kernels below are switched off or do not apply (they are asked first).  LVT_NO_PLANE_ATTENTION=1 (or
+# PLANE_ATTENTION = False) keeps the round-2 path; True forces nothing (support decides); tests pin either side.
 PLANE_ATTENTION = None
 # Round 5: in the f16x2 arithmetic the attention core runs on the flash kernels (csrc/attention_flash.hip): fp32 q / k / v / dO
 # straight from the projection GEMMs (no planes), no attention matrix in HBM (two floats per row are saved instead of 256),

@@ -9,7 +9,8 @@ import pytest
 import torch
 
 from conftest import rel_err
-from oracle import lvt_oracle as O
+from util_attention import calls, count_attention_calls
+from util_attention import reference as _reference
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -19,25 +20,6 @@ S, DA = 256, 128
 def _rand(*shape, seed=0):
     g = torch.Generator().manual_seed(seed + sum(shape))
     return torch.rand(*shape, generator=g) * 2 - 1
-
-
-def _reference(q, k, v, go, banks, blk, masked, dtype=torch.float64):
-    """-> o, m, linv, dq, dk, dv, dbanks in `dtype` on the CPU (autograd of the reference formula)."""
-    B = q.shape[0] // S
-    H = q.shape[1] // DA
-    leaves = [t.to(dtype).clone().requires_grad_(True) for t in (q, k, v)]
-    bl = [t.to(dtype).clone().requires_grad_(True) for t in banks]
-    qh, kh, vh = [t.view(B, S, H, DA).permute(0, 2, 1, 3) for t in leaves]
-    bias = O.rel_position_bias(*bl, blk).transpose(0, 1)                                # (1, H, S, S)
-    sc = qh @ kh.transpose(2, 3) / math.sqrt(DA) + bias
-    if masked:
-        sc = sc.masked_fill(torch.triu(torch.ones(S, S), 1).bool(), -1e4)
-    P = torch.softmax(sc, -1)
-    o = (P @ vh).permute(0, 2, 1, 3).reshape(B * S, H * DA)
-    o.backward(go.to(dtype))
-    m = sc.max(-1).values * math.log2(math.e)          # the kernels keep the row max in log2 units
-    linv = 1.0 / torch.exp(sc - sc.max(-1, keepdim=True).values).sum(-1)
-    return [o.detach(), m.detach().reshape(-1), linv.detach().reshape(-1)] + [t.grad for t in leaves] + [t.grad for t in bl]
 
 
 @pytest.fixture(params=[True, False], ids=["onepass", "twopass"])
@@ -142,10 +124,12 @@ def test_flash_attention_zero_rows_and_zero_gradients(blk, onepass):
 
 
 @pytest.mark.parametrize("block,masked", [((1, 16, 16), False), ((1, 16, 16), True), ((4, 8, 8), True), ((4, 8, 8), False)])
-def test_flash_layer_equals_plane_layer(block, masked):
+def test_flash_layer_equals_plane_layer(block, masked, monkeypatch):
     """One BlockLocalAttention layer through the flash kernels against the same layer through the plane kernels of
-    csrc/attention_pipe.hip (which keep the attention matrix): output and every gradient."""
+    csrc/attention_pipe.hip (which keep the attention matrix): output and every gradient.  The entry points each side went
+    through are counted: flash calls only on one side, plane calls only on the other."""
     import lvt_amd.modeling.autoregressive.vt_attention as A
+    counts = count_attention_calls(monkeypatch)
     torch.manual_seed(0)
     layer = A.BlockLocalAttention(block, 128, 512, 8, masked=masked).to(DEV)
     with torch.no_grad():
@@ -156,16 +140,20 @@ def test_flash_layer_equals_plane_layer(block, masked):
     def run(flash):
         A.FLASH_ATTENTION = flash
         try:
+            for n in counts:
+                counts[n] = 0
             for p in layer.parameters():
                 p.grad = None
             xx = x.clone().requires_grad_(True)
             y = layer.forward_tokens(xx, layer.block_size)
             y.backward(gy)
-            return [y.detach(), xx.grad] + [p.grad.clone() for p in layer.parameters()]
+            return [y.detach(), xx.grad] + [p.grad.clone() for p in layer.parameters()], dict(counts)
         finally:
             A.FLASH_ATTENTION = None
 
-    new, old = run(True), run(False)
+    (new, new_calls), (old, old_calls) = run(True), run(False)
+    assert calls(new_calls, attn_fwd_flash=1, attn_bwd_flash=1), new_calls
+    assert calls(old_calls, attn_fwd_planes=1, attn_bwd_planes=1), old_calls
     names = ["y", "dx"] + [n for n, _ in layer.named_parameters()]
     bank_scale = float(old[names.index("dh_bank")].abs().max())
     for n, a, c in zip(names, new, old):

@@ -55,7 +55,7 @@ def test_flash_bwd_lane_slots_vs_fp64(masked, onepass):
     go = go * (0.25 + torch.arange(B * S).flip(0).float().view(-1, 1) / (B * S))
     banks = [_rand(H, 2 * n - 1, seed=25 + i) * 1.5 for i, n in enumerate(blk)]
     ref = _reference(q, k, v, go, banks, blk, masked)
-    _, _, _, rdq, _, _, rdt, rdh, rdw = ref
+    _, _, _, rdq, _, _, rdt, rdh, rdw = ref[:9]                                 # (ref[9] is the attention matrix)
     # delta_i = dO_i . O_i per (sample, head, query)
     o64 = ref[0].view(B, S, H, DA)
     rdelta = (o64 * go.double().view(B, S, H, DA)).sum(-1).permute(0, 2, 1).reshape(-1)

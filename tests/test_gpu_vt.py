@@ -2,7 +2,9 @@
 reference and against the CPU oracle.  fp32 throughout; tolerances: activations / logits max-abs error
 relative to the tensor's max < 5e-5 after 16 attention layers, loss < 2e-5 relative, gradients judged
 like in test_gpu_vqvae (roundoff class, with an fp32-oracle cross-check)."""
+import contextlib
 import math
+import os
 
 import pytest
 import torch
@@ -11,6 +13,7 @@ import torch.nn.functional as F
 import seeded
 from conftest import rel_err
 from oracle import lvt_oracle as O
+from util_attention import calls, count_attention_calls
 from util_models import dsfvt_cfg
 
 pytestmark = pytest.mark.gpu
@@ -429,12 +432,46 @@ def test_fused_attention_forward(masked, blk):
     assert rel_err(P, P2) < 2e-5
 
 
-@pytest.mark.parametrize("block,masked", [((1, 16, 16), False), ((1, 16, 16), True), ((4, 8, 8), True)])
-def test_plane_attention_path_equals_default_path(block, masked):
-    """The pipelined attention kernels on bf16x3-plane operands (the default for both shipped block geometries) (csrc/attention_pipe.hip: LVT_EPI_PLANES epilogue of the
-    QKV / dO GEMMs, lvt_attn_fwd_planes, lvt_attn_bwd_planes) against the default path on one layer: output and every
-    gradient, including the bias banks reduced from per-workgroup partial sums."""
+_SWITCHES = ("FUSED_ATTENTION", "PLANE_ATTENTION", "FLASH_ATTENTION")
+_SWITCH_ENV = ("LVT_NO_FLASH_ATTENTION", "LVT_NO_PLANE_ATTENTION")
+
+
+@contextlib.contextmanager
+def _attention_path(mode, env=(), **switches):
+    """Pin everything the selector of _BlockLocalAttentionFn.forward reads -- the arithmetic, the three module switches and the
+    two LVT_NO_* variables (unset unless named in `env`) -- and put all of it back afterwards."""
     import lvt_amd.modeling.autoregressive.vt_attention as A
+    from lvt_amd.hip import binding as L
+    before = (L.get_math_mode(), {n: getattr(A, n) for n in _SWITCHES}, {n: os.environ.get(n) for n in _SWITCH_ENV})
+    try:
+        L.set_math_mode(mode)
+        for n in _SWITCHES:
+            setattr(A, n, switches.get(n, before[1][n] if n == "FUSED_ATTENTION" else None))
+        for n in _SWITCH_ENV:
+            os.environ.pop(n, None)
+            if n in env:
+                os.environ[n] = "1"
+        yield
+    finally:
+        L.set_math_mode(before[0])
+        for n, val in before[1].items():
+            setattr(A, n, val)
+        for n, val in before[2].items():
+            os.environ.pop(n, None)
+            if val is not None:
+                os.environ[n] = val
+
+
+@pytest.mark.parametrize("mode", ["bf16x3", "f16x2"])
+@pytest.mark.parametrize("block,masked", [((1, 16, 16), False), ((1, 16, 16), True), ((4, 8, 8), True), ((4, 8, 8), False)])
+def test_plane_attention_path_equals_default_path(block, masked, mode, monkeypatch):
+    """The pipelined attention kernels on bf16x3-plane operands (csrc/attention_pipe.hip: LVT_EPI_PLANES epilogue of the QKV / dO
+    GEMMs, lvt_attn_fwd_planes, lvt_attn_bwd_planes) against the round-2 path (fused forward lvt_attn_fwd, four batched GEMMs,
+    lvt_attn_softmax_bwd, bank kernel) on one layer: output and every gradient, including the bias banks reduced from
+    per-workgroup partial sums.  Both sides are pinned with the flash kernels off (in the f16x2 arithmetic they would otherwise
+    serve both), and the entry points each side went through are counted."""
+    import lvt_amd.modeling.autoregressive.vt_attention as A
+    counts = count_attention_calls(monkeypatch)
     torch.manual_seed(0)
     layer = A.BlockLocalAttention(block, 128, 512, 8, masked=masked).to(DEV)
     with torch.no_grad():
@@ -443,21 +480,79 @@ def test_plane_attention_path_equals_default_path(block, masked):
     gy = torch.randn_like(x)
 
     def run(planes):
-        A.PLANE_ATTENTION = planes
-        try:
+        with _attention_path(mode, FLASH_ATTENTION=False, PLANE_ATTENTION=planes):
+            for n in counts:
+                counts[n] = 0
             for p in layer.parameters():
                 p.grad = None
             xx = x.clone().requires_grad_(True)
             y = layer.forward_tokens(xx, layer.block_size)
             y.backward(gy)
-            return [y.detach(), xx.grad] + [p.grad.clone() for p in layer.parameters()]
-        finally:
-            A.PLANE_ATTENTION = None
+            return [y.detach(), xx.grad] + [p.grad.clone() for p in layer.parameters()], dict(counts)
 
-    new, old = run(True), run(False)
+    (new, new_calls), (old, old_calls) = run(True), run(False)
+    assert calls(new_calls, attn_fwd_planes=1, attn_bwd_planes=1), new_calls
+    assert calls(old_calls, attn_fwd=1, attn_softmax_bwd_=1), old_calls
     names = ["y", "dx"] + [n for n, _ in layer.named_parameters()]
     bank_scale = float(old[names.index("dh_bank")].abs().max())
     for n, a, c in zip(names, new, old):
         # (the gradient of a one-entry bank is sum_ij g_ij == 0 up to rounding: judged against the scale of the other banks)
         scale = bank_scale if n.endswith("_bank") else float(c.abs().max())
         assert float((a - c).abs().max()) < 2e-5 * scale + 1e-30, (n, float((a - c).abs().max()), scale)
+
+
+# What _BlockLocalAttentionFn.forward selects, row by row, derived from _use_flash / _use_planes / tx.*_supported as written:
+#   flash   <- FUSED_ATTENTION and not switched off and pairs % 8 == 0 and f16x2 and an instantiated geometry
+#   planes  <- FUSED_ATTENTION and not flash and not switched off and pairs % 8 == 0 and not f32 and an instantiated geometry
+#   fused   <- FUSED_ATTENTION and a 256-token x 128-dim block (any geometry, any pair count, any arithmetic)
+#   three   <- the QK^T GEMM, lvt_attn_softmax_fwd and the PV GEMM
+_INST, _OTHER = (1, 16, 16), (2, 8, 16)
+SELECTOR_TABLE = [
+    # mode, switches, environment, samples, heads, block -> path
+    ("f16x2", {}, (), 8, 8, _INST, "flash"),                                            # 64 pairs
+    ("f16x2", {}, (), 1, 8, _INST, "flash"),                                            # 8 pairs: the smallest launch
+    ("f16x2", {}, (), 1, 8, (4, 8, 8), "flash"),
+    ("f16x2", dict(FLASH_ATTENTION=False), (), 8, 8, _INST, "planes"),
+    ("f16x2", {}, ("LVT_NO_FLASH_ATTENTION",), 1, 8, _INST, "planes"),
+    ("f16x2", {}, ("LVT_NO_PLANE_ATTENTION",), 1, 8, _INST, "flash"),                   # (the plane switch does not reach flash)
+    ("f16x2", dict(FLASH_ATTENTION=False, PLANE_ATTENTION=False), (), 1, 8, _INST, "fused"),
+    ("f16x2", {}, ("LVT_NO_FLASH_ATTENTION", "LVT_NO_PLANE_ATTENTION"), 1, 8, _INST, "fused"),
+    ("bf16x3", {}, (), 8, 8, _INST, "planes"),
+    ("bf16x3", {}, (), 1, 8, (4, 8, 8), "planes"),
+    ("bf16x3", dict(PLANE_ATTENTION=False), (), 1, 8, _INST, "fused"),
+    ("bf16x3", {}, ("LVT_NO_PLANE_ATTENTION",), 1, 8, _INST, "fused"),
+    ("f32", {}, (), 8, 8, _INST, "fused"),
+    ("f32", dict(PLANE_ATTENTION=True, FLASH_ATTENTION=True), (), 1, 8, _INST, "fused"),  # True forces nothing: support decides
+    ("f16x2", {}, (), 1, 4, _INST, "fused"),                                            # 4 pairs, each arithmetic
+    ("bf16x3", {}, (), 1, 4, _INST, "fused"),
+    ("f32", {}, (), 1, 4, _INST, "fused"),
+    ("f16x2", {}, (), 3, 4, _INST, "fused"),                                            # 12 pairs: no multiple of 8
+    ("f16x2", {}, (), 1, 8, _OTHER, "fused"),                                           # 256 tokens, no instantiated geometry
+    ("bf16x3", {}, (), 1, 8, _OTHER, "fused"),
+    ("f16x2", dict(FUSED_ATTENTION=False), (), 1, 8, _INST, "three"),
+    ("bf16x3", dict(FUSED_ATTENTION=False), (), 1, 8, _INST, "three"),
+    ("f32", dict(FUSED_ATTENTION=False), (), 1, 4, _INST, "three"),
+]
+_PATH_CALLS = dict(flash=dict(attn_fwd_flash=1), planes=dict(attn_fwd_planes=1), fused=dict(attn_fwd=1), three=dict(attn_softmax_fwd_=1))
+
+
+def test_selector_table(monkeypatch):
+    """One layer, forward only, for each row of SELECTOR_TABLE: exactly the entry point of the expected path runs."""
+    import lvt_amd.modeling.autoregressive.vt_attention as A
+    counts = count_attention_calls(monkeypatch)
+    torch.manual_seed(0)
+    layers = {}
+    for mode, switches, env, b, heads, block, path in SELECTOR_TABLE:
+        row = (mode, switches, env, b, heads, block)
+        if (heads, block) not in layers:
+            layers[heads, block] = A.BlockLocalAttention(block, 128, 512, heads, masked=True).to(DEV)
+        layer = layers[heads, block]
+        x = torch.randn(b * 256, 512, device=DEV)
+        for n in counts:
+            counts[n] = 0
+        with _attention_path(mode, env=env, **switches), torch.no_grad():
+            y = layer.forward_tokens(x, block)
+        assert torch.isfinite(y).all(), row
+        assert calls(counts, **_PATH_CALLS[path]), (row, path, counts)
+    assert A.FLASH_ATTENTION is None and A.PLANE_ATTENTION is None and A.FUSED_ATTENTION is True
+
