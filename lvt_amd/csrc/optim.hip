@@ -7,6 +7,7 @@
 // norm behind the clip coefficient comes from lvt_grad_sqnorm / lvt_grad_clip_coef below.
 #include "lvt_common.h"
 #include <math.h>
+#include <type_traits>
 
 typedef lvt_opt_entry LvtOptEntry;   // declared in lvt_hip.h; mirrored by ctypes in lvt_amd/hip/binding.py
 #define OPT_CHUNK 16384
@@ -23,6 +24,19 @@ __device__ __forceinline__ int find_tensor(const OptArgs &a, int blk) {
     while (t + 1 < a.n && a.chunk_prefix[t + 1] <= blk) ++t;
     return t;
 }
+
+// What a workgroup works on: tensor t of the launch's table, its entry e, and elements [lo, hi) of it (one chunk).
+struct OptChunk {
+    int t;
+    LvtOptEntry e;
+    long long lo, hi;
+    __device__ __forceinline__ explicit OptChunk(const OptArgs &a) {
+        t = find_tensor(a, blockIdx.x);
+        e = a.e[t];
+        lo = (long long)(blockIdx.x - a.chunk_prefix[t]) * OPT_CHUNK;
+        hi = min(e.n, lo + OPT_CHUNK);
+    }
+};
 
 // float4 lanes when the chunk of every stream of the tensor is 16-byte aligned and the tensor length is a multiple of 4
 __device__ __forceinline__ bool opt_vec_ok(const LvtOptEntry &e, long long lo) {
@@ -87,10 +101,8 @@ __device__ __forceinline__ void adam_body(const OptArgs &a, float beta1, float b
         if (gscale->skip) return;           // non-finite gradient norm: no store, p / s0 / s1 keep their bits
         coef = gscale->coef;
     }
-    const int t = find_tensor(a, blockIdx.x);
-    const LvtOptEntry e = a.e[t];
-    const long long lo = (long long)(blockIdx.x - a.chunk_prefix[t]) * OPT_CHUNK;
-    const long long hi = min(e.n, lo + OPT_CHUNK);
+    const OptChunk c(a);
+    const LvtOptEntry &e = c.e;
     const float step = e.lr / bc1;
     auto upd = [&](float g, float p, float &m, float &v) -> float {
         if (SCALED) g = clipped_grad(g, coef, clamp);
@@ -100,10 +112,10 @@ __device__ __forceinline__ void adam_body(const OptArgs &a, float beta1, float b
         const float denom = sqrtf(v) / bc2_sqrt + eps;
         return p - step * (m / denom);
     };
-    float *const sh = EMA ? ema[t] : nullptr;
+    float *const sh = EMA ? ema[c.t] : nullptr;
     const bool sh_vec = EMA && ((uintptr_t)sh & 15) == 0;
-    if (opt_vec_ok(e, lo)) {                // 16-byte lanes: a wave instruction moves 1 KB instead of 256 B
-        for (long long i = lo + 4 * threadIdx.x; i < hi; i += 1024) {
+    if (opt_vec_ok(e, c.lo)) {              // 16-byte lanes: a wave instruction moves 1 KB instead of 256 B
+        for (long long i = c.lo + 4 * threadIdx.x; i < c.hi; i += 1024) {
             const float4 g4 = *reinterpret_cast<const float4 *>(e.g + i), p4 = *reinterpret_cast<const float4 *>(e.p + i);
             float4 m4 = *reinterpret_cast<const float4 *>(e.s0 + i), v4 = *reinterpret_cast<const float4 *>(e.s1 + i), o;
             o.x = upd(g4.x, p4.x, m4.x, v4.x); o.y = upd(g4.y, p4.y, m4.y, v4.y);
@@ -114,13 +126,13 @@ __device__ __forceinline__ void adam_body(const OptArgs &a, float beta1, float b
         }
         return;
     }
-    for (long long i = lo + threadIdx.x; i < hi; i += 256) {
+    for (long long i = c.lo + threadIdx.x; i < c.hi; i += 256) {
         float m = e.s0[i], v = e.s1[i];
         const float o = upd(e.g[i], e.p[i], m, v);
         e.p[i] = o;
         e.s0[i] = m; e.s1[i] = v;
     }
-    if (EMA) ema_follow_scalar(sh, e.p, lo, hi, w);
+    if (EMA) ema_follow_scalar(sh, e.p, c.lo, c.hi, w);
 }
 
 __global__ __launch_bounds__(256) void lvt_adam_kernel(const OptArgs a, float beta1, float beta2, float eps,
@@ -149,10 +161,8 @@ __device__ __forceinline__ void rmsprop_body(const OptArgs &a, float alpha, floa
         if (gscale->skip) return;
         coef = gscale->coef;
     }
-    const int t = find_tensor(a, blockIdx.x);
-    const LvtOptEntry e = a.e[t];
-    const long long lo = (long long)(blockIdx.x - a.chunk_prefix[t]) * OPT_CHUNK;
-    const long long hi = min(e.n, lo + OPT_CHUNK);
+    const OptChunk c(a);
+    const LvtOptEntry &e = c.e;
     auto upd = [&](float g, float p, float &sq, float &buf) -> float {
         if (SCALED) g = clipped_grad(g, coef, clamp);
         if (e.wd != 0.f) g += e.wd * p;
@@ -162,10 +172,10 @@ __device__ __forceinline__ void rmsprop_body(const OptArgs &a, float alpha, floa
         return p - e.lr * (g / avg);
     };
     const bool mom = momentum > 0.f;
-    float *const sh = EMA ? ema[t] : nullptr;
+    float *const sh = EMA ? ema[c.t] : nullptr;
     const bool sh_vec = EMA && ((uintptr_t)sh & 15) == 0;
-    if (opt_vec_ok(e, lo)) {
-        for (long long i = lo + 4 * threadIdx.x; i < hi; i += 1024) {
+    if (opt_vec_ok(e, c.lo)) {
+        for (long long i = c.lo + 4 * threadIdx.x; i < c.hi; i += 1024) {
             const float4 g4 = *reinterpret_cast<const float4 *>(e.g + i), p4 = *reinterpret_cast<const float4 *>(e.p + i);
             float4 s4 = *reinterpret_cast<const float4 *>(e.s0 + i), o;
             float4 b4 = mom ? *reinterpret_cast<const float4 *>(e.s1 + i) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -178,14 +188,14 @@ __device__ __forceinline__ void rmsprop_body(const OptArgs &a, float alpha, floa
         }
         return;
     }
-    for (long long i = lo + threadIdx.x; i < hi; i += 256) {
+    for (long long i = c.lo + threadIdx.x; i < c.hi; i += 256) {
         float sq = e.s0[i], buf = mom ? e.s1[i] : 0.f;
         const float o = upd(e.g[i], e.p[i], sq, buf);
         e.p[i] = o;
         e.s0[i] = sq;
         if (mom) e.s1[i] = buf;
     }
-    if (EMA) ema_follow_scalar(sh, e.p, lo, hi, w);
+    if (EMA) ema_follow_scalar(sh, e.p, c.lo, c.hi, w);
 }
 
 __global__ __launch_bounds__(256) void lvt_rmsprop_kernel(const OptArgs a, float alpha, float eps, float momentum) {
@@ -205,19 +215,17 @@ __global__ __launch_bounds__(256) void lvt_rmsprop_ema_kernel(const EmaArgs a, f
 
 // Exchange of the contents of e.p and e.s0 (lvt_ema_swap): the chunking of the steps, float4 lanes when both sides allow.
 __global__ __launch_bounds__(256) void lvt_ema_swap_kernel(const OptArgs a) {
-    const int t = find_tensor(a, blockIdx.x);
-    const LvtOptEntry e = a.e[t];
-    const long long lo = (long long)(blockIdx.x - a.chunk_prefix[t]) * OPT_CHUNK;
-    const long long hi = min(e.n, lo + OPT_CHUNK);
+    const OptChunk c(a);
+    const LvtOptEntry &e = c.e;
     if ((((uintptr_t)e.p | (uintptr_t)e.s0) & 15) == 0 && (e.n & 3) == 0) {
-        for (long long i = lo + 4 * threadIdx.x; i < hi; i += 1024) {
+        for (long long i = c.lo + 4 * threadIdx.x; i < c.hi; i += 1024) {
             const float4 x = *reinterpret_cast<const float4 *>(e.p + i), y = *reinterpret_cast<const float4 *>(e.s0 + i);
             *reinterpret_cast<float4 *>(e.p + i) = y;
             *reinterpret_cast<float4 *>(e.s0 + i) = x;
         }
         return;
     }
-    for (long long i = lo + threadIdx.x; i < hi; i += 256) {
+    for (long long i = c.lo + threadIdx.x; i < c.hi; i += 256) {
         const float x = e.p[i], y = e.s0[i];
         e.p[i] = y;
         e.s0[i] = x;
@@ -238,19 +246,17 @@ __device__ __forceinline__ double block_sum_f64(double v, double *scratch) {
 // one workgroup per 16384-element chunk, like the steps; only e.g and e.n of the table are set
 __global__ __launch_bounds__(256) void lvt_grad_sqnorm_kernel(const OptArgs a, double *partials) {
     __shared__ double scratch[4];
-    const int t = find_tensor(a, blockIdx.x);
-    const LvtOptEntry e = a.e[t];
-    const long long lo = (long long)(blockIdx.x - a.chunk_prefix[t]) * OPT_CHUNK;
-    const long long hi = min(e.n, lo + OPT_CHUNK);
+    const OptChunk c(a);
+    const LvtOptEntry &e = c.e;
     double acc = 0.0;
     auto sq = [&](float g) { const double d = (double)g; acc += d * d; };
-    if (opt_vec_ok(e, lo)) {
-        for (long long i = lo + 4 * threadIdx.x; i < hi; i += 1024) {
+    if (opt_vec_ok(e, c.lo)) {
+        for (long long i = c.lo + 4 * threadIdx.x; i < c.hi; i += 1024) {
             const float4 g4 = *reinterpret_cast<const float4 *>(e.g + i);
             sq(g4.x); sq(g4.y); sq(g4.z); sq(g4.w);
         }
     } else {
-        for (long long i = lo + threadIdx.x; i < hi; i += 256) sq(e.g[i]);
+        for (long long i = c.lo + threadIdx.x; i < c.hi; i += 256) sq(e.g[i]);
     }
     const double total = block_sum_f64(acc, scratch);
     if (threadIdx.x == 0) partials[blockIdx.x] = total;
@@ -275,169 +281,166 @@ __global__ __launch_bounds__(256) void lvt_grad_clip_coef_kernel(const double *p
     }
 }
 
-template <typename Launch>
-static int for_each_group(const LvtOptEntry *host, int n, Launch launch) {
-    for (int base = 0; base < n; base += OPT_MAXT) {
-        OptArgs a;
-        a.n = (n - base) < OPT_MAXT ? (n - base) : OPT_MAXT;
-        int blocks = 0;
-        for (int i = 0; i < a.n; ++i) {
-            a.e[i] = host[base + i];
-            if (!a.e[i].p || !a.e[i].g || !a.e[i].s0 || a.e[i].n <= 0) {
-                lvt_set_error("optimizer: bad entry %d", base + i);
-                return LVT_EINVAL;
+// ---- host: a list of n tensors becomes launches of up to OPT_MAXT tensors each ------------------------------------------------
+static OptArgs &opt_table(OptArgs &a) { return a; }
+static OptArgs &opt_table(EmaArgs &a) { return a.a; }
+
+// The one place where that happens, for every entry point of this file (`who`, named in the messages).  Args: OptArgs or EmaArgs.
+// fill(args, i, src) -> LVT_OK or an error: validates entry `src` of the caller's list and writes it to slot i of the table
+// (p, g, s0, s1, n, lr, wd as the kernel needs them, and the shadow slot of an EmaArgs); chunk_prefix is filled here.
+// launch(args, blocks, done): `done` chunks went out with the slices before this one.
+// The whole list is validated before the first launch: a refused call has launched nothing.
+template <typename Args, typename Fill, typename Launch>
+static int launch_slices(const char *who, int n, Fill fill, Launch launch) {
+    for (int pass = 0; pass < 2; ++pass) {                    // 0: validate every slice, 1: build them again and launch
+        long long done = 0;
+        for (int base = 0; base < n; base += OPT_MAXT) {
+            Args args = {};
+            OptArgs &a = opt_table(args);
+            a.n = (n - base) < OPT_MAXT ? (n - base) : OPT_MAXT;
+            long long blocks = 0;
+            for (int i = 0; i < a.n; ++i) {
+                const int rc = fill(args, i, base + i);
+                if (rc != LVT_OK) return rc;
+                a.chunk_prefix[i] = (int)blocks;
+                blocks += lvt_cdiv(a.e[i].n, OPT_CHUNK);
+                LVT_REQUIRE(blocks < (1ll << 31), "%s: too many chunks in one launch", who);
             }
-            a.chunk_prefix[i] = blocks;
-            blocks += (int)lvt_cdiv(a.e[i].n, OPT_CHUNK);
+            a.chunk_prefix[a.n] = (int)blocks;
+            if (pass == 0) continue;
+            launch(args, (unsigned)blocks, done);
+            LVT_CHECK_LAUNCH(who);
+            done += blocks;
         }
-        a.chunk_prefix[a.n] = blocks;
-        launch(a, blocks);
-        LVT_CHECK_LAUNCH("optimizer kernel");
     }
     return LVT_OK;
 }
 
-// p, exp_avg (s0), exp_avg_sq (s1) updated in place; `step` is the 1-based step count of these tensors.
-extern "C" int lvt_adam_step(const LvtOptEntry *host, int n, float beta1, float beta2, float eps, int step,
-                             void *stream) {
-    LVT_REQUIRE(host && n > 0 && step > 0, "adam_step: bad args");
+// The slices of a step: entry `src` of the host table, and its shadow when the launch carries shadows (Args = EmaArgs).
+template <typename Args, typename Launch>
+static int step_slices(const char *who, const LvtOptEntry *host, float *const *ema, int n, Launch launch) {
+    return launch_slices<Args>(
+        who, n,
+        [&](Args &args, int i, int src) -> int {
+            const LvtOptEntry &e = opt_table(args).e[i] = host[src];
+            LVT_REQUIRE(e.p && e.g && e.s0 && e.n > 0, "%s: bad entry %d (null p, g or s0, or no elements)", who, src);
+            if constexpr (std::is_same<Args, EmaArgs>::value) {
+                float *sh = args.ema[i] = ema[src];
+                LVT_REQUIRE(sh && (((uintptr_t)sh) & 3) == 0 && sh != e.p,
+                            "%s: bad shadow %d (null, misaligned, or the parameter itself)", who, src);
+            }
+            return LVT_OK;
+        },
+        launch);
+}
+
+// One launcher per optimizer behind its three entry points: `ema` (nullable) selects the kernels that carry shadows, a clip
+// (`gscale`, `clamp` or both) the scaled body.  p, exp_avg (s0), exp_avg_sq (s1) updated in place; `step` is the 1-based step
+// count of these tensors.
+static int adam_launch(const char *who, const LvtOptEntry *host, float *const *ema, int n, float beta1, float beta2, float eps,
+                       int step, const lvt_clip_record *gscale, float clamp, float w, void *stream) {
+    LVT_REQUIRE(host && n > 0 && step > 0, "%s: bad args", who);
     hipStream_t s = (hipStream_t)stream;
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    return for_each_group(host, n, [&](const OptArgs &a, int blocks) {
-        hipLaunchKernelGGL(lvt_adam_kernel, dim3(blocks), dim3(256), 0, s, a, beta1, beta2, eps, (float)bc1,
-                           (float)sqrt(bc2));
+    const double bc1d = 1.0 - pow((double)beta1, step), bc2d = 1.0 - pow((double)beta2, step);
+    const float bc1 = (float)bc1d, bc2_sqrt = (float)sqrt(bc2d);
+    const bool scaled = gscale || clamp > 0.f;
+    if (ema)
+        return step_slices<EmaArgs>(who, host, ema, n, [&](const EmaArgs &a, unsigned blocks, long long) {
+            auto kernel = scaled ? lvt_adam_ema_kernel<true> : lvt_adam_ema_kernel<false>;
+            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, a, beta1, beta2, eps, bc1, bc2_sqrt, gscale, clamp, w);
+        });
+    return step_slices<OptArgs>(who, host, nullptr, n, [&](const OptArgs &a, unsigned blocks, long long) {
+        if (scaled)
+            hipLaunchKernelGGL(lvt_adam_scaled_kernel, dim3(blocks), dim3(256), 0, s, a, beta1, beta2, eps, bc1, bc2_sqrt, gscale, clamp);
+        else
+            hipLaunchKernelGGL(lvt_adam_kernel, dim3(blocks), dim3(256), 0, s, a, beta1, beta2, eps, bc1, bc2_sqrt);
     });
 }
 
 // p, square_avg (s0), momentum_buffer (s1, may be NULL when momentum == 0) updated in place.
-extern "C" int lvt_rmsprop_step(const LvtOptEntry *host, int n, float alpha, float eps, float momentum,
-                                void *stream) {
-    LVT_REQUIRE(host && n > 0, "rmsprop_step: bad args");
+static int rmsprop_launch(const char *who, const LvtOptEntry *host, float *const *ema, int n, float alpha, float eps,
+                          float momentum, const lvt_clip_record *gscale, float clamp, float w, void *stream) {
+    LVT_REQUIRE(host && n > 0, "%s: bad args", who);
     hipStream_t s = (hipStream_t)stream;
-    return for_each_group(host, n, [&](const OptArgs &a, int blocks) {
-        hipLaunchKernelGGL(lvt_rmsprop_kernel, dim3(blocks), dim3(256), 0, s, a, alpha, eps, momentum);
+    const bool scaled = gscale || clamp > 0.f;
+    if (ema)
+        return step_slices<EmaArgs>(who, host, ema, n, [&](const EmaArgs &a, unsigned blocks, long long) {
+            auto kernel = scaled ? lvt_rmsprop_ema_kernel<true> : lvt_rmsprop_ema_kernel<false>;
+            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, a, alpha, eps, momentum, gscale, clamp, w);
+        });
+    return step_slices<OptArgs>(who, host, nullptr, n, [&](const OptArgs &a, unsigned blocks, long long) {
+        if (scaled)
+            hipLaunchKernelGGL(lvt_rmsprop_scaled_kernel, dim3(blocks), dim3(256), 0, s, a, alpha, eps, momentum, gscale, clamp);
+        else
+            hipLaunchKernelGGL(lvt_rmsprop_kernel, dim3(blocks), dim3(256), 0, s, a, alpha, eps, momentum);
     });
 }
 
-#define REQUIRE_CLIP_ARGS(name)                                                                                              \
-    LVT_REQUIRE(clamp >= 0.f && clamp < __builtin_inff() && (gscale || clamp > 0.f) && (((uintptr_t)gscale) & 15) == 0,      \
-                name ": needs a 16-byte aligned gscale record, a finite clamp > 0, or both")
+// The clip of a step: a 16-byte aligned record, a finite clamp > 0, or both.  The *_scaled entries refuse a call with neither
+// (the plain entries are for that); the *_ema entries take it (`optional`) and then launch the unscaled body.
+#define REQUIRE_CLIP_ARGS(name, optional)                                                                                    \
+    LVT_REQUIRE(clamp >= 0.f && clamp < __builtin_inff() && (((uintptr_t)gscale) & 15) == 0 &&                               \
+                    ((optional) || gscale || clamp > 0.f),                                                                   \
+                name ": gscale must be 16-byte aligned and clamp finite and >= 0%s", (optional) ? "" : ", one of them given")
+#define REQUIRE_EMA_ARGS(name)                                                                                               \
+    LVT_REQUIRE(ema, name ": null shadow table");                                                                            \
+    LVT_REQUIRE(w >= 0.f && w <= 1.f, name ": w = 1 - decay must lie in [0, 1]");                                            \
+    REQUIRE_CLIP_ARGS(name, true)
+
+extern "C" int lvt_adam_step(const LvtOptEntry *host, int n, float beta1, float beta2, float eps, int step,
+                             void *stream) {
+    return adam_launch("adam_step", host, nullptr, n, beta1, beta2, eps, step, nullptr, 0.f, 0.f, stream);
+}
+
+extern "C" int lvt_rmsprop_step(const LvtOptEntry *host, int n, float alpha, float eps, float momentum,
+                                void *stream) {
+    return rmsprop_launch("rmsprop_step", host, nullptr, n, alpha, eps, momentum, nullptr, 0.f, 0.f, stream);
+}
 
 extern "C" int lvt_adam_step_scaled(const LvtOptEntry *host, int n, float beta1, float beta2, float eps, int step,
                                     const lvt_clip_record *gscale, float clamp, void *stream) {
-    LVT_REQUIRE(host && n > 0 && step > 0, "adam_step_scaled: bad args");
-    REQUIRE_CLIP_ARGS("adam_step_scaled");
-    hipStream_t s = (hipStream_t)stream;
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    return for_each_group(host, n, [&](const OptArgs &a, int blocks) {
-        hipLaunchKernelGGL(lvt_adam_scaled_kernel, dim3(blocks), dim3(256), 0, s, a, beta1, beta2, eps, (float)bc1,
-                           (float)sqrt(bc2), gscale, clamp);
-    });
+    REQUIRE_CLIP_ARGS("adam_step_scaled", false);
+    return adam_launch("adam_step_scaled", host, nullptr, n, beta1, beta2, eps, step, gscale, clamp, 0.f, stream);
 }
 
 extern "C" int lvt_rmsprop_step_scaled(const LvtOptEntry *host, int n, float alpha, float eps, float momentum,
                                        const lvt_clip_record *gscale, float clamp, void *stream) {
-    LVT_REQUIRE(host && n > 0, "rmsprop_step_scaled: bad args");
-    REQUIRE_CLIP_ARGS("rmsprop_step_scaled");
-    hipStream_t s = (hipStream_t)stream;
-    return for_each_group(host, n, [&](const OptArgs &a, int blocks) {
-        hipLaunchKernelGGL(lvt_rmsprop_scaled_kernel, dim3(blocks), dim3(256), 0, s, a, alpha, eps, momentum, gscale, clamp);
-    });
+    REQUIRE_CLIP_ARGS("rmsprop_step_scaled", false);
+    return rmsprop_launch("rmsprop_step_scaled", host, nullptr, n, alpha, eps, momentum, gscale, clamp, 0.f, stream);
 }
 
 // ---- Polyak-averaged weights inside the steps ---------------------------------------------------------------------------------
-template <typename Launch>
-static int for_each_group_ema(const LvtOptEntry *host, float *const *ema, int n, Launch launch) {
-    for (int base = 0; base < n; base += OPT_MAXT) {
-        EmaArgs a;
-        a.a.n = (n - base) < OPT_MAXT ? (n - base) : OPT_MAXT;
-        int blocks = 0;
-        for (int i = 0; i < a.a.n; ++i) {
-            a.a.e[i] = host[base + i];
-            a.ema[i] = ema[base + i];
-            if (!a.a.e[i].p || !a.a.e[i].g || !a.a.e[i].s0 || a.a.e[i].n <= 0) {
-                lvt_set_error("optimizer: bad entry %d", base + i);
-                return LVT_EINVAL;
-            }
-            if (!a.ema[i] || (((uintptr_t)a.ema[i]) & 3) || a.ema[i] == a.a.e[i].p) {
-                lvt_set_error("optimizer: bad shadow %d (null, misaligned, or the parameter itself)", base + i);
-                return LVT_EINVAL;
-            }
-            a.a.chunk_prefix[i] = blocks;
-            blocks += (int)lvt_cdiv(a.a.e[i].n, OPT_CHUNK);
-        }
-        for (int i = a.a.n; i < OPT_MAXT; ++i) a.ema[i] = nullptr;
-        a.a.chunk_prefix[a.a.n] = blocks;
-        launch(a, blocks);
-        LVT_CHECK_LAUNCH("optimizer kernel");
-    }
-    return LVT_OK;
-}
-
-#define REQUIRE_EMA_ARGS(name)                                                                                               \
-    LVT_REQUIRE(ema, name ": null shadow table");                                                                            \
-    LVT_REQUIRE(w >= 0.f && w <= 1.f, name ": w = 1 - decay must lie in [0, 1]");                                            \
-    LVT_REQUIRE(clamp >= 0.f && clamp < __builtin_inff() && (((uintptr_t)gscale) & 15) == 0,                                 \
-                name ": gscale must be 16-byte aligned and clamp finite and >= 0")
-
 extern "C" int lvt_adam_step_ema(const LvtOptEntry *host, float *const *ema, int n, float beta1, float beta2, float eps,
                                  int step, float w, const lvt_clip_record *gscale, float clamp, void *stream) {
-    LVT_REQUIRE(host && n > 0 && step > 0, "adam_step_ema: bad args");
     REQUIRE_EMA_ARGS("adam_step_ema");
-    hipStream_t s = (hipStream_t)stream;
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    const bool scaled = gscale || clamp > 0.f;
-    return for_each_group_ema(host, ema, n, [&](const EmaArgs &a, int blocks) {
-        if (scaled)
-            hipLaunchKernelGGL(lvt_adam_ema_kernel<true>, dim3(blocks), dim3(256), 0, s, a, beta1, beta2, eps, (float)bc1,
-                               (float)sqrt(bc2), gscale, clamp, w);
-        else
-            hipLaunchKernelGGL(lvt_adam_ema_kernel<false>, dim3(blocks), dim3(256), 0, s, a, beta1, beta2, eps, (float)bc1,
-                               (float)sqrt(bc2), gscale, clamp, w);
-    });
+    return adam_launch("adam_step_ema", host, ema, n, beta1, beta2, eps, step, gscale, clamp, w, stream);
 }
 
 extern "C" int lvt_rmsprop_step_ema(const LvtOptEntry *host, float *const *ema, int n, float alpha, float eps, float momentum,
                                     float w, const lvt_clip_record *gscale, float clamp, void *stream) {
-    LVT_REQUIRE(host && n > 0, "rmsprop_step_ema: bad args");
     REQUIRE_EMA_ARGS("rmsprop_step_ema");
-    hipStream_t s = (hipStream_t)stream;
-    const bool scaled = gscale || clamp > 0.f;
-    return for_each_group_ema(host, ema, n, [&](const EmaArgs &a, int blocks) {
-        if (scaled)
-            hipLaunchKernelGGL(lvt_rmsprop_ema_kernel<true>, dim3(blocks), dim3(256), 0, s, a, alpha, eps, momentum, gscale,
-                               clamp, w);
-        else
-            hipLaunchKernelGGL(lvt_rmsprop_ema_kernel<false>, dim3(blocks), dim3(256), 0, s, a, alpha, eps, momentum, gscale,
-                               clamp, w);
-    });
+    return rmsprop_launch("rmsprop_step_ema", host, ema, n, alpha, eps, momentum, gscale, clamp, w, stream);
 }
 
 extern "C" int lvt_ema_swap(float *const *pa, float *const *pb, const long long *counts, int n, void *stream) {
     LVT_REQUIRE(pa && pb && counts && n > 0, "ema_swap: bad args");
     hipStream_t s = (hipStream_t)stream;
-    for (int base = 0; base < n; base += OPT_MAXT) {
-        OptArgs a = {};
-        a.n = (n - base) < OPT_MAXT ? (n - base) : OPT_MAXT;
-        long long blocks = 0;
-        for (int i = 0; i < a.n; ++i) {
-            float *x = pa[base + i], *y = pb[base + i];
-            const long long cnt = counts[base + i];
+    return launch_slices<OptArgs>(
+        "ema_swap", n,
+        [&](OptArgs &a, int i, int src) -> int {
+            float *x = pa[src], *y = pb[src];
+            const long long cnt = counts[src];
             LVT_REQUIRE(x && y && x != y && cnt > 0 && ((((uintptr_t)x) | ((uintptr_t)y)) & 3) == 0,
-                        "ema_swap: bad entry %d (null, misaligned or identical pointers, or no elements)", base + i);
-            LVT_REQUIRE((x + cnt <= y) || (y + cnt <= x), "ema_swap: entry %d overlaps itself", base + i);
+                        "ema_swap: bad entry %d (null, misaligned or identical pointers, or no elements)", src);
+            LVT_REQUIRE((x + cnt <= y) || (y + cnt <= x), "ema_swap: entry %d overlaps itself", src);
             a.e[i].p = x;
             a.e[i].s0 = y;
             a.e[i].n = cnt;
-            a.chunk_prefix[i] = (int)blocks;
-            blocks += lvt_cdiv(cnt, OPT_CHUNK);
-        }
-        LVT_REQUIRE(blocks < (1ll << 31), "ema_swap: too many chunks in one launch");
-        a.chunk_prefix[a.n] = (int)blocks;
-        hipLaunchKernelGGL(lvt_ema_swap_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
-        LVT_CHECK_LAUNCH("ema_swap kernel");
-    }
-    return LVT_OK;
+            return LVT_OK;
+        },
+        [&](const OptArgs &a, unsigned blocks, long long) {
+            hipLaunchKernelGGL(lvt_ema_swap_kernel, dim3(blocks), dim3(256), 0, s, a);
+        });
 }
 
 extern "C" long long lvt_grad_sqnorm_partials(const lvt_grad_entry *host, int n) {
@@ -452,28 +455,20 @@ extern "C" long long lvt_grad_sqnorm_partials(const lvt_grad_entry *host, int n)
 
 extern "C" int lvt_grad_sqnorm(const lvt_grad_entry *host, int n, double *partials, long long n_partials, void *stream) {
     LVT_REQUIRE(host && n > 0 && partials && (((uintptr_t)partials) & 7) == 0, "grad_sqnorm: bad args");
-    const long long need = lvt_grad_sqnorm_partials(host, n);
+    const long long need = lvt_grad_sqnorm_partials(host, n);             // validates every entry
     LVT_REQUIRE(need > 0, "grad_sqnorm: bad entry (null or misaligned gradient, or no elements)");
     LVT_REQUIRE(need == n_partials, "grad_sqnorm: %lld partials for entries that need %lld", n_partials, need);
     hipStream_t s = (hipStream_t)stream;
-    long long done = 0;                                   // chunks of the launches before this one
-    for (int base = 0; base < n; base += OPT_MAXT) {
-        OptArgs a = {};
-        a.n = (n - base) < OPT_MAXT ? (n - base) : OPT_MAXT;
-        long long blocks = 0;
-        for (int i = 0; i < a.n; ++i) {
-            a.e[i].g = host[base + i].g;
-            a.e[i].n = host[base + i].n;
-            a.chunk_prefix[i] = (int)blocks;
-            blocks += lvt_cdiv(a.e[i].n, OPT_CHUNK);
-        }
-        LVT_REQUIRE(blocks < (1ll << 31), "grad_sqnorm: too many chunks in one launch");
-        a.chunk_prefix[a.n] = (int)blocks;
-        hipLaunchKernelGGL(lvt_grad_sqnorm_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, partials + done);
-        LVT_CHECK_LAUNCH("grad_sqnorm kernel");
-        done += blocks;
-    }
-    return LVT_OK;
+    return launch_slices<OptArgs>(
+        "grad_sqnorm", n,
+        [&](OptArgs &a, int i, int src) -> int {
+            a.e[i].g = host[src].g;
+            a.e[i].n = host[src].n;
+            return LVT_OK;
+        },
+        [&](const OptArgs &a, unsigned blocks, long long done) {
+            hipLaunchKernelGGL(lvt_grad_sqnorm_kernel, dim3(blocks), dim3(256), 0, s, a, partials + done);
+        });
 }
 
 extern "C" int lvt_grad_clip_coef(const double *partials, long long n_partials, float max_norm, lvt_clip_record *record,

@@ -15,7 +15,7 @@ unclipped gradient.  The step count of a skipped step still advances (`state["st
 import torch
 
 from ..hip import binding as L
-from .fused import _FusedBase
+from .fused import require_fused, walk_parameters
 
 CLIP_TYPES = ("norm", "value")
 
@@ -33,28 +33,23 @@ class GradClipper:
     def __init__(self, optimizers, clip_type="norm", clip_value=1.0, norm_type=2.0):
         check_clip_args(clip_type, clip_value, norm_type)
         self.optimizers = list(optimizers)
-        for opt in self.optimizers:
-            if not isinstance(opt, _FusedBase):
-                raise L.LvtError("gradient clipping lives in the fused optimizers' step kernels; got %s (there is no CPU path)"
-                                 % type(opt).__name__)
+        require_fused(self.optimizers,
+                      "gradient clipping lives in the fused optimizers' step kernels; got %s (there is no CPU path)")
         self.clip_type, self.clip_value = clip_type, float(clip_value)
         self.record = self.norm = self.coef = self.skip = self.skipped = None        # device tensors, made by the first prepare()
 
     def _gradients(self):
         """Gradients of all parameters in optimizer, group and parameter order; shared parameters once, absent gradients left out."""
-        grads, seen = [], set()
-        for opt in self.optimizers:
-            for group in opt.param_groups:
-                for p in group["params"]:
-                    g = p.grad
-                    if g is None or id(p) in seen:
-                        continue
-                    seen.add(id(p))
-                    if not g.is_cuda:
-                        raise L.LvtError("gradient clipping needs gradients on a MI355X; there is no CPU path")
-                    if g.is_sparse or not g.is_contiguous() or g.dtype != torch.float32:
-                        raise L.LvtError("gradient clipping needs dense contiguous float32 gradients")
-                    grads.append(g)
+        grads = []
+        for _, _, p in walk_parameters(self.optimizers):
+            g = p.grad
+            if g is None:
+                continue
+            if not g.is_cuda:
+                raise L.LvtError("gradient clipping needs gradients on a MI355X; there is no CPU path")
+            if g.is_sparse or not g.is_contiguous() or g.dtype != torch.float32:
+                raise L.LvtError("gradient clipping needs dense contiguous float32 gradients")
+            grads.append(g)
         return grads
 
     def _state(self, device):

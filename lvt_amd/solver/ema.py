@@ -22,7 +22,8 @@ import os
 import torch
 
 from ..hip import binding as L
-from .fused import _FusedBase, check_ema_decay, ema_decay_at  # noqa: F401  (ema_decay_at: part of this module's interface)
+from .fused import check_ema_decay, ema_decay_at  # noqa: F401  (ema_decay_at: part of this module's interface)
+from .fused import require_fused, walk_parameters
 
 
 def ema_twin(path):
@@ -35,10 +36,8 @@ class ModelEma:
     def __init__(self, optimizers, decay=0.9999, warmup=True):
         check_ema_decay(decay)
         self.optimizers = [o["optimizer"] if isinstance(o, dict) else o for o in optimizers]
-        for opt in self.optimizers:
-            if not isinstance(opt, _FusedBase):
-                raise L.LvtError("averaged weights live in the fused optimizers' step kernels; got %s (there is no CPU path)"
-                                 % type(opt).__name__)
+        require_fused(self.optimizers,
+                      "averaged weights live in the fused optimizers' step kernels; got %s (there is no CPU path)")
         self.decay, self.warmup = float(decay), bool(warmup)
         for opt in self.optimizers:
             opt.enable_ema(self.decay, self.warmup)
@@ -51,22 +50,17 @@ class ModelEma:
     def _pairs(self):
         """(parameter, shadow) of every parameter of every optimizer, shared parameters once.  A parameter that has not been
         stepped yet has no state: its average is the parameter itself, and the shadow it will start from is made here."""
-        pairs, seen = [], set()
-        for opt in self.optimizers:
-            for group in opt.param_groups:
-                for p in group["params"]:
-                    if id(p) in seen:
-                        continue
-                    seen.add(id(p))
-                    st = opt.state.get(p)
-                    if st is not None and "ema" in st:
-                        e = st["ema"]
-                    else:
-                        init = opt.__dict__.setdefault("_ema_init", {})
-                        if p not in init:
-                            init[p] = p.detach().clone(memory_format=torch.preserve_format)
-                        e = init[p]
-                    pairs.append((p, e))
+        pairs = []
+        for opt, _, p in walk_parameters(self.optimizers):
+            st = opt.state.get(p)
+            if st is not None and "ema" in st:
+                e = st["ema"]
+            else:
+                init = opt.__dict__.setdefault("_ema_init", {})
+                if p not in init:
+                    init[p] = p.detach().clone(memory_format=torch.preserve_format)
+                e = init[p]
+            pairs.append((p, e))
         return pairs
 
     def shadows(self, module=None):

@@ -57,6 +57,9 @@ def _shadows(tensors, ents):
 
 
 class _FusedBase(Optimizer):
+    """`step()` and everything around it.  An optimizer supplies `_entry` (the name of its plain C entry point; `_scaled` and
+    `_ema` are appended), `_make_state(st, p, group)`, `_batch_item(st, group)` -> (hyper-parameter key, s0, s1) -- the one
+    call `step()` makes per parameter -- and `_hyper(key, step)` -> the arguments between the table and the clip."""
     _clip = None            # (record tensor or None, clamp) for the next step(): set_grad_clip
     _ema = None             # (decay, warmup) once enable_ema was called
     ema_updates = 0         # updates launched since enable_ema (a skipped step counts: the count lives on the host)
@@ -122,105 +125,113 @@ class _FusedBase(Optimizer):
                     p.grad.detach_()
                     p.grad.zero_()
 
-    def _collect(self, make_state):
-        """-> dict step_count -> list of (p, grad, s0, s1, lr, wd)."""
-        by_step = {}
+    def _collect(self):
+        """-> {step count: {hyper-parameter key: ([(p, grad, s0, s1, lr, wd)], [shadow])}}: the launches of a `step()`, both
+        levels in first-seen order; the shadows only while averaging is on.  This loop is the host cost of a step (269 tensors
+        for DSFVT): one hook call per parameter, no second pass."""
+        by_step, state, averaging, batch_item = {}, self.state, self._ema is not None, self._batch_item
         for group in self.param_groups:
             for p in group["params"]:
-                if p.grad is None:
+                g = p.grad
+                if g is None:
                     continue
                 if not p.is_cuda:
                     raise L.LvtError("fused optimizers need parameters on a MI355X; there is no CPU path")
-                g = p.grad
                 if g.is_sparse or not g.is_contiguous() or not p.is_contiguous():
                     raise L.LvtError("fused optimizers need dense contiguous parameters and gradients")
-                st = self.state[p]
+                st = state[p]
                 if len(st) == 0:
-                    make_state(st, p, group)
-                if self._ema is not None and "ema" not in st:
+                    st["step"] = 0
+                    self._make_state(st, p, group)
+                if averaging and "ema" not in st:
                     st["ema"] = self._new_shadow(p)
                 st["step"] += 1
-                by_step.setdefault(int(st["step"]), []).append((p, g, st, group))
+                key, s0, s1 = batch_item(st, group)
+                step = int(st["step"])
+                batches = by_step.get(step)
+                if batches is None:
+                    batches = by_step[step] = {}
+                batch = batches.get(key)
+                if batch is None:
+                    batch = batches[key] = ([], [])
+                batch[0].append((p, g, s0, s1, group["lr"], group["weight_decay"]))
+                if averaging:
+                    batch[1].append(st["ema"])
         return by_step
-
-
-class FusedAdam(_FusedBase):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
 
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
-
-        def make(st, p, group):
-            st["step"] = 0
-            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
         clip, w, launched = self._take_clip(), self._ema_weight(), False
-        for step, items in self._collect(make).items():
-            # groups may differ in betas/eps in principle; batch by (betas, eps)
-            batches, shadows = {}, {}
-            for p, g, st, group in items:
-                key = (group["betas"], group["eps"])
-                batches.setdefault(key, []).append((p, g, st["exp_avg"], st["exp_avg_sq"], group["lr"],
-                                                    group["weight_decay"]))
-                if w is not None:
-                    shadows.setdefault(key, []).append(st.get("ema"))
-            for (betas, eps), ents in batches.items():
-                arr = _entries(ents)
+        for step, batches in self._collect().items():
+            for key, (ents, shadows) in batches.items():
+                arr, n, hyper = _entries(ents), len(ents), self._hyper(key, step)
                 launched = True
                 if w is not None:
                     record, clamp = clip if clip is not None else (None, 0.0)
-                    L.check(L.lib().lvt_adam_step_ema(arr, _shadows(shadows[(betas, eps)], ents), len(ents), betas[0], betas[1],
-                                                      eps, step, w, L.ptr(record), clamp, L.stream_ptr()), "lvt_adam_step_ema")
+                    name, args = self._entry + "_ema", (arr, _shadows(shadows, ents), n) + hyper + (w, L.ptr(record), clamp)
                 elif clip is None:
-                    L.check(L.lib().lvt_adam_step(arr, len(ents), betas[0], betas[1], eps, step, L.stream_ptr()),
-                            "lvt_adam_step")
+                    name, args = self._entry, (arr, n) + hyper
                 else:
-                    L.check(L.lib().lvt_adam_step_scaled(arr, len(ents), betas[0], betas[1], eps, step, L.ptr(clip[0]),
-                                                         clip[1], L.stream_ptr()), "lvt_adam_step_scaled")
+                    name, args = self._entry + "_scaled", (arr, n) + hyper + (L.ptr(clip[0]), clip[1])
+                L.check(getattr(L.lib(), name)(*args, L.stream_ptr()), name)
         if w is not None and launched:
             self.ema_updates += 1
         L.bump_epoch()          # parameters were rewritten through raw pointers: cached max |.| records are stale
         return loss
 
 
+def walk_parameters(optimizers):
+    """(optimizer, group, parameter) in optimizer, group and parameter order; a parameter that appears twice is yielded once."""
+    seen = set()
+    for opt in optimizers:
+        for group in opt.param_groups:
+            for p in group["params"]:
+                if id(p) not in seen:
+                    seen.add(id(p))
+                    yield opt, group, p
+
+
+def require_fused(optimizers, message):
+    """What lives in the step kernels has no other home: `message` (with one %s for the class name) for any other optimizer."""
+    for opt in optimizers:
+        if not isinstance(opt, _FusedBase):
+            raise L.LvtError(message % type(opt).__name__)
+
+
+class FusedAdam(_FusedBase):
+    _entry = "lvt_adam_step"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    def _make_state(self, st, p, group):
+        st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+
+    def _batch_item(self, st, group):
+        # groups may differ in betas/eps in principle; batch by (betas, eps)
+        return (group["betas"], group["eps"]), st["exp_avg"], st["exp_avg_sq"]
+
+    def _hyper(self, key, step):
+        (beta1, beta2), eps = key
+        return beta1, beta2, eps, step
+
+
 class FusedRMSprop(_FusedBase):
+    _entry = "lvt_rmsprop_step"
+
     def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0, momentum=0):
         super().__init__(params, dict(lr=lr, alpha=alpha, eps=eps, weight_decay=weight_decay, momentum=momentum,
                                       centered=False))
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
+    def _make_state(self, st, p, group):
+        st["square_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        if group["momentum"] > 0:
+            st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
 
-        def make(st, p, group):
-            st["step"] = 0
-            st["square_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            if group["momentum"] > 0:
-                st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-        clip, w, launched = self._take_clip(), self._ema_weight(), False
-        for step, items in self._collect(make).items():
-            batches, shadows = {}, {}
-            for p, g, st, group in items:
-                key = (group["alpha"], group["eps"], group["momentum"])
-                batches.setdefault(key, []).append((p, g, st["square_avg"], st.get("momentum_buffer"), group["lr"],
-                                                    group["weight_decay"]))
-                if w is not None:
-                    shadows.setdefault(key, []).append(st.get("ema"))
-            for (alpha, eps, mom), ents in batches.items():
-                arr = _entries(ents)
-                launched = True
-                if w is not None:
-                    record, clamp = clip if clip is not None else (None, 0.0)
-                    L.check(L.lib().lvt_rmsprop_step_ema(arr, _shadows(shadows[(alpha, eps, mom)], ents), len(ents), alpha, eps,
-                                                         mom, w, L.ptr(record), clamp, L.stream_ptr()), "lvt_rmsprop_step_ema")
-                elif clip is None:
-                    L.check(L.lib().lvt_rmsprop_step(arr, len(ents), alpha, eps, mom, L.stream_ptr()), "lvt_rmsprop_step")
-                else:
-                    L.check(L.lib().lvt_rmsprop_step_scaled(arr, len(ents), alpha, eps, mom, L.ptr(clip[0]), clip[1],
-                                                            L.stream_ptr()), "lvt_rmsprop_step_scaled")
-        if w is not None and launched:
-            self.ema_updates += 1
-        L.bump_epoch()
-        return loss
+    def _batch_item(self, st, group):
+        return (group["alpha"], group["eps"], group["momentum"]), st["square_avg"], st.get("momentum_buffer")
+
+    def _hyper(self, key, step):
+        return key                          # (alpha, eps, momentum): RMSprop does not read the step count

@@ -39,3 +39,42 @@ def test_fused_matches_torch(kind):
         assert rel_err(pa, pb) < 2e-6
     sa, sb = oa.state_dict()["state"], ob.state_dict()["state"]
     assert set(sa[0].keys()) == set(sb[0].keys())
+
+
+@pytest.mark.parametrize("kind", ["adam", "rmsprop"])
+def test_two_keys_and_two_step_counts_in_one_optimizer(kind):
+    """Launch grouping and order: one optimizer whose groups carry two hyper-parameter keys, 70 ragged tensors each (two launches
+    per batch), half of each key's tensors joining at step 3, so that every `step()` from there on launches two step counts
+    times two keys.  Against torch built with the same groups, and bit for bit against a second run."""
+    from lvt_amd.solver.fused import FusedAdam, FusedRMSprop
+    dev = "cuda:0"
+    if kind == "adam":
+        keys, fused, ref = [dict(betas=(0.9, 0.9), eps=1e-8), dict(betas=(0.8, 0.95), eps=1e-6)], FusedAdam, torch.optim.Adam
+    else:
+        keys, fused, ref = [dict(alpha=0.95, momentum=0.9), dict(alpha=0.9, momentum=0.0)], FusedRMSprop, torch.optim.RMSprop
+    # parameter i: tensor i // 2 of key i % 2 (the keys alternate, one group per parameter, like the reference)
+    init = [t for pair in zip(_params(1)[:70], _params(2)[:70]) for t in pair]
+    late = [(i // 2) % 2 == 1 for i in range(len(init))]
+    grads = [[torch.randn(t.shape, generator=torch.Generator().manual_seed(1000 * step + i)).to(dev) for i, t in enumerate(init)]
+             for step in range(5)]
+
+    def run(cls):
+        ps = [torch.nn.Parameter(t.clone().to(dev)) for t in init]
+        opt = cls([dict(params=[p], lr=1e-2 * (1 + i % 3), weight_decay=0.0 if (i // 2) % 2 else 1e-3, **keys[i % 2])
+                   for i, p in enumerate(ps)], 1e-2)
+        for step in range(5):
+            for i, p in enumerate(ps):
+                p.grad = None if late[i] and step < 2 else grads[step][i].clone()
+            opt.step()
+        return ps, opt
+
+    (a, oa), (a2, oa2), (b, _) = run(fused), run(fused), run(ref)
+    assert sorted(int(oa.state[p]["step"]) for p in a[:4]) == [3, 3, 5, 5]
+    for pa, pb in zip(a, b):
+        assert rel_err(pa, pb) < 2e-6
+    for pa, pa2 in zip(a, a2):
+        assert torch.equal(pa, pa2)
+        sa, sa2 = oa.state[pa], oa2.state[pa2]
+        assert set(sa) == set(sa2)
+        for k, v in sa.items():
+            assert torch.equal(v, sa2[k]) if torch.is_tensor(v) else v == sa2[k], k

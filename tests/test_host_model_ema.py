@@ -134,6 +134,33 @@ def test_abi_table_and_argument_validation():
     assert lib.lvt_ema_swap(None, b, n, 1, None) == -1 and lib.lvt_ema_swap(a, b, None, 1, None) == -1
 
 
+def test_a_bad_entry_behind_the_first_launch_is_refused_before_any_launch():
+    """70 entries are two launches (64 + 6).  Entry 66 is bad: the call must name it and return LVT_EINVAL -- had the first 64
+    been launched before the table was read to its end, the launch (of fake pointers; without a GPU, of anything) would have
+    failed differently, or worse, run."""
+    from lvt_amd.hip import binding as L
+    lib = L.lib()
+    vp, cll = C.c_void_p, C.c_longlong
+    n, bad = 70, 66
+    at = lambda i, k: ((i + 1) << 20) + 4096 * k                     # noqa: E731  (stream k of tensor i: 1 MB apart, 16-byte aligned)
+    o = (L.OptEntry * n)()
+    for i in range(n):
+        o[i].p, o[i].g, o[i].s0, o[i].s1, o[i].n, o[i].lr = at(i, 0), at(i, 1), at(i, 2), at(i, 3), 8, 1e-3
+    o[bad].g = None
+    sh = (vp * n)(*[at(i, 4) for i in range(n)])
+    for name, call in (("adam_step", lambda: lib.lvt_adam_step(o, n, 0.9, 0.9, 1e-8, 1, None)),
+                       ("rmsprop_step_scaled", lambda: lib.lvt_rmsprop_step_scaled(o, n, 0.9, 1e-8, 0.0, None, 0.5, None)),
+                       ("adam_step_ema", lambda: lib.lvt_adam_step_ema(o, sh, n, 0.9, 0.9, 1e-8, 1, 0.1, None, 0.0, None))):
+        assert call() == -1, name
+        err = lib.lvt_last_error()
+        assert b"66" in err and name.encode() in err, err
+    a, b = (vp * n)(*[at(i, 0) for i in range(n)]), (vp * n)(*[at(i, 1) for i in range(n)])
+    b[bad] = at(bad, 0) + 16                                          # b[66] starts 16 bytes into the 32 of a[66]
+    assert lib.lvt_ema_swap(a, b, (cll * n)(*[8] * n), n, None) == -1
+    err = lib.lvt_last_error()
+    assert b"66" in err and b"ema_swap" in err, err
+
+
 def test_shadow_table_refuses_a_wrong_count():
     """The pointer table handed to the `_ema` entry points has one shadow per entry: anything else is an error, not a launch."""
     from lvt_amd.hip import LvtError
