@@ -707,8 +707,16 @@ __device__ __forceinline__ long long patcht_orow(int row, int cls) {
     return (long long)(row >> 8) * 1024 + (2 * y + (cls >> 1)) * 32 + 2 * x + (cls & 1);
 }
 
-struct PatchRows { __device__ __forceinline__ long long operator()(int row) const { return patch_orow(row); } };
-struct PatchTRows { int cls; __device__ __forceinline__ long long operator()(int row) const { return patcht_orow(row, cls); } };
+// (LANE_STEP, epilogue_fast.h: the 4 rows of an aligned group are the `e` above -- consecutive x, and every second x of the phase)
+struct PatchRows {
+    static constexpr int LANE_STEP = 1;
+    __device__ __forceinline__ long long operator()(int row) const { return patch_orow(row); }
+};
+struct PatchTRows {
+    static constexpr int LANE_STEP = 2;
+    int cls;
+    __device__ __forceinline__ long long operator()(int row) const { return patcht_orow(row, cls); }
+};
 
 // ------------------------------------------------------------------------------------------------
 // epilogue shared by the kernels: alpha / bias / residual / ReLU / tanh / sigmoid / mask / accumulate, or split-K partials
@@ -1183,7 +1191,7 @@ __global__ __launch_bounds__(NTHREADS, (MATH == 2 ? 2 : 1)) void lvt_gemm_kernel
             if (p.splits > 1) {
                 e.C = p.partial; e.ldc = p.N; e.coff = split * p.partial_stride + (long long)z * p.M * p.N; e.alpha = 1.f; e.flags = 0;
                 e.bias = nullptr; e.res = nullptr; e.ldr = 0; e.mask = nullptr; e.ldm = 0;
-                (void)lvt_epi_fast_wave<0, TM, TN>(e, acc, wave_tile, m0 + wm * (TM * 32), n0 + wn * (TN * 32), lane);
+                (void)lvt_epi_fast_pick<0, TM, TN>(e, acc, wave_tile, m0 + wm * (TM * 32), n0 + wn * (TN * 32), lane);
                 return;
             }
             const unsigned seen = lvt_amax_peek(p.c_amax);
@@ -1748,7 +1756,7 @@ __global__ __launch_bounds__(WIDE_THREADS, 2) void lvt_gemm_wide_kernel(const KP
         if (p.splits > 1) {
             e.C = p.partial; e.ldc = p.N; e.coff = tc.split * p.partial_stride + (long long)tc.z * p.M * p.N; e.alpha = 1.f; e.flags = 0;
             e.bias = nullptr; e.res = nullptr; e.ldr = 0; e.mask = nullptr; e.ldm = 0;
-            (void)lvt_epi_fast_wave<0, TM, TN>(e, acc, wave_tile, m0 + wm * (TM * 32), n0 + wn * (TN * 32), lane);
+            (void)lvt_epi_fast_pick<0, TM, TN>(e, acc, wave_tile, m0 + wm * (TM * 32), n0 + wn * (TN * 32), lane);
             return;
         }
         const unsigned seen = lvt_amax_peek(p.c_amax);
