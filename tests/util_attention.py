@@ -1,4 +1,5 @@
-"""Shared by the attention kernel tests (test_gpu_flash_attention.py, test_gpu_plane_attention.py, test_gpu_decode_kernels.py):
+"""Shared by the attention kernel tests (test_gpu_flash_attention.py, test_gpu_flash_matrix.py, test_gpu_plane_attention.py,
+test_gpu_decode_kernels.py):
 the fp64 autograd evaluation of the reference formula for one 256-token x 128-dim block layer
 (vidgen/modeling/autoregressive/vt_attention.py:59-81 with the bias of :169-174), the exact 3-way bf16 split that the plane
 kernels take their operands in, and the acceptance rule of the attention tests."""
@@ -17,16 +18,17 @@ def rand(*shape, seed=0):
     return torch.rand(*shape, generator=g) * 2 - 1
 
 
-def reference(q, k, v, go, banks, blk, masked, dtype=torch.float64):
+def reference(q, k, v, go, banks, blk, masked, dtype=torch.float64, temper=None):
     """-> o, m, linv, dq, dk, dv, dbanks (3), P in `dtype` on the CPU (autograd of the reference formula).  q / k / v / go are
-    token-major (B*S, H*DA), P is (B, H, S, S)."""
+    token-major (B*S, H*DA), P is (B, H, S, S).  temper: what the scores are divided by (None: sqrt(DA), the layer's value)."""
     B = q.shape[0] // S
     H = q.shape[1] // DA
+    temper = math.sqrt(DA) if temper is None else temper
     leaves = [t.to(dtype).clone().requires_grad_(True) for t in (q, k, v)]
     bl = [t.to(dtype).clone().requires_grad_(True) for t in banks]
     qh, kh, vh = [t.view(B, S, H, DA).permute(0, 2, 1, 3) for t in leaves]
     bias = O.rel_position_bias(*bl, blk).transpose(0, 1)                                # (1, H, S, S)
-    sc = qh @ kh.transpose(2, 3) / math.sqrt(DA) + bias
+    sc = qh @ kh.transpose(2, 3) / temper + bias
     if masked:
         sc = sc.masked_fill(torch.triu(torch.ones(S, S), 1).bool(), -1e4)
     P = torch.softmax(sc, -1)

@@ -1,5 +1,5 @@
 """NaN-payload guard buffers shared by the kernel conformance tests (test_gpu_gemm_matrix.py, test_gpu_attention_fallback.py,
-test_gpu_row_kernels.py).
+test_gpu_row_kernels.py, test_gpu_plane_attention.py, test_gpu_flash_matrix.py).
 
 A `Buf` holds its logical elements inside a buffer that is otherwise filled with one recognisable quiet-NaN bit pattern, PAD
 elements before and after: a kernel that writes outside its logical output changes payload bits (`outside_untouched`), and one
@@ -15,13 +15,20 @@ PAYLOAD = 0x7FC0DEAD                       # a quiet NaN with a recognisable man
 IPAYLOAD = 0x7FC0DEAD7FC0DEAD              # the int64 buffers repeat it (read as two floats: the same NaN twice)
 
 
-class Buf:
-    """A NaN-payload buffer (PAD floats before and after) holding `values` at element offsets `idx` (same shape)."""
+def float_bits(x):
+    """The int32 bit pattern of the fp32 value x (a `payload` for Buf)."""
+    return int(torch.tensor([x], dtype=torch.float32).view(torch.int32))
 
-    def __init__(self, idx, values=None, dtype=torch.float32, start=PAD):
-        self.idx, self.start = idx, start
+
+class Buf:
+    """A NaN-payload buffer (PAD floats before and after) holding `values` at element offsets `idx` (same shape).  `payload`:
+    another int32 bit pattern for everything that is not a logical element.  A row maximum built with fmaxf drops a NaN, so
+    padding that leaked into one shows only with a finite payload (float_bits(3.0e38): the row's scale swallows it)."""
+
+    def __init__(self, idx, values=None, dtype=torch.float32, start=PAD, payload=PAYLOAD):
+        self.idx, self.start, self.payload = idx, start, payload
         n = (int(idx.max()) + 1) if idx.numel() else 0
-        host = torch.full((start + n + PAD,), PAYLOAD, dtype=torch.int32).view(torch.float32)
+        host = torch.full((start + n + PAD,), payload, dtype=torch.int32).view(torch.float32)
         if values is not None:
             host[start + idx.reshape(-1)] = values.reshape(-1).float()
         self.dev = host.to(DEV)
@@ -36,7 +43,7 @@ class Buf:
         bits = self.dev.cpu().view(torch.int32)
         keep = torch.ones(bits.numel(), dtype=torch.bool)
         keep[self.start + self.idx.reshape(-1)] = False
-        return bool((bits[keep] == PAYLOAD).all())
+        return bool((bits[keep] == self.payload).all())
 
     def bits(self):
         return self.dev.cpu().view(torch.int32)
