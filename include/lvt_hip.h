@@ -424,6 +424,13 @@ int lvt_l1_fwd(const float *a, const float *b, long long n, double denom, float 
                void *workspace, size_t workspace_bytes, void *stream);
 int lvt_l1_bwd(const float *a, const float *b, long long n, double denom, float scale,
                const float *gout_dev, const float *add, int tanh_of_a, float *out, float *out_amax, void *stream);
+/* the two backwards with one more operand pair (additive under ABI 680): out = gout[0] c (a - b | sign(a - b)) + g2[0] G, c as
+ * above, G a gradient of a second loss term w.r.t. the same tensor (lvt_ssim_loss_fwd), g2 the device scalar autograd hands back for
+ * that term (both required).  One tensor, one max |out| record.                                             */
+int lvt_mse_bwd_plus(const float *a, const float *b, long long n, double denom, float scale, const float *gout_dev,
+                     const float *g2_dev, const float *G, float *out, float *out_amax, void *stream);
+int lvt_l1_bwd_plus(const float *a, const float *b, long long n, double denom, float scale, const float *gout_dev,
+                    const float *g2_dev, const float *G, float *out, float *out_amax, void *stream);
 int lvt_tanh_bwd(const float *g, const float *y, long long n, float *out, float *out_amax, void *stream);
 /* out = g * y * (1 - y), y the saved sigmoid output (ABI 650); out_amax as on lvt_tanh_bwd                */
 int lvt_sigmoid_bwd(const float *g, const float *y, long long n, float *out, float *out_amax, void *stream);
@@ -777,6 +784,25 @@ int lvt_frame_quality(const float *a, const float *b, int F, int C, int H, int W
                       long long n_partials, void *stream);
 int lvt_frame_quality_finish(const double *partials, int F, int C, int H, int W, double data_range, long long n_partials,
                              double *frames, double *acc, void *stream);
+
+/* ---- SSIM term of the reconstruction loss (additive under ABI 680; csrc/ssim_loss.hip; the rule in plain torch:
+ * lvt_amd/evaluation/quality.py ssim_loss_reference).  xt, x: fp32 channels-last frames (N, 1, H, W, Cp), Cp = C rounded up to 4,
+ * pad channels zero, 16-byte aligned, any H, W >= 11.  mean, stdv: C device floats; SSIM (the rule of lvt_frame_quality) is taken
+ * of v * stdv[c] + mean[c] with C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2.  Two launches on one stream:
+ *   1. lvt_ssim_loss_fwd: one workgroup per (frame, channel quad, 16 x 16 tile of pixels) -> partials[i] = the sum of the SSIM map
+ *      over the tile's own positions (fp64, plain stores).  G (nullable, shaped like xt): d loss / d xt, pad channels exact 0, with
+ *      n = N C (H-10) (W-10) the factor -lam / n and stdv[c] applied; every workgroup recomputes the 10-position halo of map
+ *      positions its pixels collect from.  Without G the backward half is skipped and the partials have the same bits.
+ *   2. lvt_ssim_loss_finish: one workgroup, fixed order: out[0] = lam * (1 - sum / n) in fp32.
+ * n_partials must equal lvt_ssim_loss_partials (host arithmetic: N (Cp / 4) ceil(H / 16) ceil(W / 16); -1 for a shape that is
+ * refused).  A null or misaligned pointer, N or C <= 0, Cp that is not C rounded up to 4, H or W below 11, a data_range that is not
+ * positive and finite, a lam that is negative or not finite, another n_partials: LVT_EINVAL before any device work.  No atomics:
+ * the same inputs give the same bits; bitwise-equal planes give a loss of exactly 0 and a G of exact zeros. */
+long long lvt_ssim_loss_partials(int N, int H, int W, int Cp);
+int lvt_ssim_loss_fwd(const float *xt, const float *x, int N, int H, int W, int Cp, int C, const float *mean, const float *stdv,
+                      double data_range, double lam, double *partials, long long n_partials, float *G, void *stream);
+int lvt_ssim_loss_finish(const double *partials, long long n_partials, int N, int H, int W, int C, double lam, float *out,
+                         void *stream);
 
 #ifdef __cplusplus
 }

@@ -108,6 +108,7 @@ _TABLE = [
     ('LOSS.PIXEL.ONN', False),
     ('LOSS.PIXEL.LAMBDA', 1.0),
     ('LOSS.PIXEL.MODE', 'l2'),
+    ('LOSS.SSIM.LAMBDA', 0.0),                       # weight of the 1 - SSIM term of the reconstruction loss; 0.0: off
     ('LOSS.GAN.ONN', False),
     ('LOSS.GAN.LAMBDA_G', 1.0),
     ('LOSS.GAN.LAMBDA_D', 1.0),

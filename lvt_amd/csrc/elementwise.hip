@@ -156,13 +156,17 @@ extern "C" int lvt_l1_fwd(const float *a, const float *b, long long n, double de
 }
 
 // out = add + g * (2*scale/denom) * (a - b) [* (1 - a^2)]      g = gout_dev[0] (or 1)
-template <int L1>          // L1 = 1: sign(a - b) instead of (a - b) (torch's l1_loss backward: 0 at a == b)
+// PLUS = 1 (lvt_mse_bwd_plus / lvt_l1_bwd_plus): one more operand pair, out = g * c * (a - b | sign) + g2[0] * G -- the gradient of
+// a second loss term on the same tensor (the SSIM term, csrc/ssim_loss.hip) merged in the launch that reports max |out|
+template <int L1, int PLUS = 0>          // L1 = 1: sign(a - b) instead of (a - b) (torch's l1_loss backward: 0 at a == b)
 __global__ void lvt_mse_bwd_kernel(const float *__restrict__ a, const float *__restrict__ b, long long n4, float c,
                                    const float *__restrict__ gout, const float *__restrict__ add, int tanh_of_a,
-                                   float *__restrict__ out, float *__restrict__ out_amax) {
+                                   float *__restrict__ out, float *__restrict__ out_amax, const float *__restrict__ g2 = nullptr,
+                                   const float *__restrict__ G = nullptr) {
     __shared__ float amax_scratch[4];
     float am = 0.f;
     const float g = (gout ? gout[0] : 1.0f) * c;
+    const float h = PLUS ? g2[0] : 0.f;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
          i += (long long)gridDim.x * blockDim.x) {
         const float4 x = reinterpret_cast<const float4 *>(a)[i];
@@ -171,6 +175,10 @@ __global__ void lvt_mse_bwd_kernel(const float *__restrict__ a, const float *__r
         if (L1) r = make_float4((float)((r.x > 0.f) - (r.x < 0.f)), (float)((r.y > 0.f) - (r.y < 0.f)), (float)((r.z > 0.f) - (r.z < 0.f)),
                                 (float)((r.w > 0.f) - (r.w < 0.f)));
         r.x *= g; r.y *= g; r.z *= g; r.w *= g;
+        if (PLUS) {
+            const float4 z = reinterpret_cast<const float4 *>(G)[i];
+            r.x = __fmaf_rn(h, z.x, r.x); r.y = __fmaf_rn(h, z.y, r.y); r.z = __fmaf_rn(h, z.z, r.z); r.w = __fmaf_rn(h, z.w, r.w);
+        }
         if (tanh_of_a) {
             r.x *= 1.f - x.x * x.x; r.y *= 1.f - x.y * x.y; r.z *= 1.f - x.z * x.z; r.w *= 1.f - x.w * x.w;
         }
@@ -198,6 +206,23 @@ extern "C" int lvt_l1_bwd(const float *a, const float *b, long long n, double de
     hipLaunchKernelGGL(lvt_mse_bwd_kernel<1>, dim3(grid_for(n / 4, 256, out_amax ? 2048 : 8192)), dim3(256), 0, (hipStream_t)stream, a, b,
                        n / 4, (float)((double)scale / denom), gout_dev, add, tanh_of_a, out, out_amax);
     LVT_CHECK_LAUNCH("lvt_mse_bwd_kernel<l1>");
+    return LVT_OK;
+}
+// out = gout[0] * (2*scale/denom) * (a - b) + g2[0] * G, and the l1 form: the same kernel with one more operand pair
+extern "C" int lvt_mse_bwd_plus(const float *a, const float *b, long long n, double denom, float scale, const float *gout_dev,
+                                const float *g2_dev, const float *G, float *out, float *out_amax, void *stream) {
+    LVT_REQUIRE(a && b && out && g2_dev && G && n > 0 && n % 4 == 0 && denom > 0, "mse_bwd_plus: bad args");
+    hipLaunchKernelGGL((lvt_mse_bwd_kernel<0, 1>), dim3(grid_for(n / 4, 256, out_amax ? 2048 : 8192)), dim3(256), 0, (hipStream_t)stream,
+                       a, b, n / 4, (float)(2.0 * (double)scale / denom), gout_dev, (const float *)nullptr, 0, out, out_amax, g2_dev, G);
+    LVT_CHECK_LAUNCH("lvt_mse_bwd_kernel<plus>");
+    return LVT_OK;
+}
+extern "C" int lvt_l1_bwd_plus(const float *a, const float *b, long long n, double denom, float scale, const float *gout_dev,
+                               const float *g2_dev, const float *G, float *out, float *out_amax, void *stream) {
+    LVT_REQUIRE(a && b && out && g2_dev && G && n > 0 && n % 4 == 0 && denom > 0, "l1_bwd_plus: bad args");
+    hipLaunchKernelGGL((lvt_mse_bwd_kernel<1, 1>), dim3(grid_for(n / 4, 256, out_amax ? 2048 : 8192)), dim3(256), 0, (hipStream_t)stream,
+                       a, b, n / 4, (float)((double)scale / denom), gout_dev, (const float *)nullptr, 0, out, out_amax, g2_dev, G);
+    LVT_CHECK_LAUNCH("lvt_mse_bwd_kernel<l1, plus>");
     return LVT_OK;
 }
 

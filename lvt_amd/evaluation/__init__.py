@@ -1,6 +1,6 @@
 from .evaluator import (BitsEvaluator, CodesExtractor, DatasetEvaluator, DatasetEvaluators, FrameQualityEvaluator, MSEEvaluator,
                         VTSampler, build_evaluator, inference_on_dataset)
-from .quality import frame_quality_reference
+from .quality import frame_quality_reference, ssim_loss_reference
 
 __all__ = ["BitsEvaluator", "CodesExtractor", "DatasetEvaluator", "DatasetEvaluators", "FrameQualityEvaluator", "MSEEvaluator",
-           "VTSampler", "build_evaluator", "frame_quality_reference", "inference_on_dataset"]
+           "VTSampler", "build_evaluator", "frame_quality_reference", "inference_on_dataset", "ssim_loss_reference"]

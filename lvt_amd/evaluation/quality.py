@@ -9,7 +9,10 @@ the data range; the SSIM of a frame is the mean of the map over all its channels
 `skimage.metrics.structural_similarity(gaussian_weights=True, use_sample_covariance=False)` and the default of `pytorch_msssim`
 (neither is a dependency of this package, and neither was at hand to compare with).
 
-PSNR of a frame is 10 log10(L^2 / mse) with the mse over all channels of the frame; a frame with mse == 0 has none (+inf)."""
+PSNR of a frame is 10 log10(L^2 / mse) with the mse over all channels of the frame; a frame with mse == 0 has none (+inf).
+
+`ssim_loss_reference` states the SSIM term of the reconstruction loss (LOSS.SSIM.LAMBDA, csrc/ssim_loss.hip) with the
+same windows and constants, and `ssim_loss_closed_form` its gradient without autograd."""
 import math
 
 import torch
@@ -66,3 +69,69 @@ def frame_quality_reference(a, b, data_range, dtype=torch.float64):
     sxy = windowed(x * y, win) - mx * my
     ssim = ((2 * (mx * my) + c1) * (2 * sxy + c2)) / ((mx * mx + my * my + c1) * (sxx + syy + c2))
     return psnr, ssim.mean(dim=(1, 2, 3))
+
+
+def ssim_loss_reference(x, y, mean, std, data_range, lam):
+    """The SSIM term of the reconstruction loss (LOSS.SSIM.LAMBDA): the rule the gfx950 kernel behind
+    `lvt_amd.hip.ew.ssim_loss_fwd` is tested against (csrc/ssim_loss.hip).  x (the reconstruction, not clamped) and y (the target)
+    are (F, C, H, W) frames in the network's normalised space, in any float dtype and on any device; `mean`, `std`: C values
+    that take them back to pixel space, u = v * std[c] + mean[c] (SSIM's luminance term assumes non-negative intensities).
+    -> the scalar lam * (1 - mean over frames, channels and map positions of SSIM(u(x), u(y))), differentiable in x (and y),
+    with the SSIM of `frame_quality_reference`: its windows, moments and constants, evaluated in the dtype of x."""
+    x, y = check_frames(x, y, data_range)
+    C = x.shape[1]
+    if len(mean) != C or len(std) != C:
+        raise ValueError("ssim loss: %d channels, %d means and %d stds" % (C, len(mean), len(std)))
+    dt, dev = x.dtype, x.device
+    m = torch.as_tensor(mean, dtype=torch.float64).to(dtype=dt, device=dev).view(1, C, 1, 1)
+    s = torch.as_tensor(std, dtype=torch.float64).to(dtype=dt, device=dev).view(1, C, 1, 1)
+    ux, uy = x * s + m, y.to(dt) * s + m
+    L = float(data_range)
+    win = gaussian_window(dt, dev)
+    c1, c2 = (0.01 * L) ** 2, (0.03 * L) ** 2
+    mx, my = windowed(ux, win), windowed(uy, win)
+    sxx = windowed(ux * ux, win) - mx * mx
+    syy = windowed(uy * uy, win) - my * my
+    sxy = windowed(ux * uy, win) - mx * my
+    ssim = ((2 * (mx * my) + c1) * (2 * sxy + c2)) / ((mx * mx + my * my + c1) * (sxx + syy + c2))
+    return lam * (1 - ssim.mean())
+
+
+def ssim_loss_closed_form(x, y, mean, std, data_range, lam):
+    """d ssim_loss_reference / d x in closed form, without autograd: with the windowed moments of u(x), u(y) and
+    A1 = 2 mx my + C1, A2 = 2 sxy + C2, B1 = mx^2 + my^2 + C1, B2 = sxx + syy + C2, S = A1 A2 / (B1 B2),
+        dA1 = A2 / (B1 B2), dA2 = A1 / (B1 B2), dB1 = -S / B1, dB2 = -S / B2
+        alpha = 2 my (dA1 - dA2) + 2 mx (dB1 - dB2), beta = 2 dB2, gamma = 2 dA2
+        dS_total / du_x = W^T alpha + u_x W^T beta + u_y W^T gamma
+    (W^T: the transpose of `windowed`, a full 11-tap pass in each direction), times -lam / (F C (H-10) (W-10)) and std[c]."""
+    x, y = check_frames(x, y, data_range)
+    F_, C, H, W = x.shape
+    dt, dev = x.dtype, x.device
+    m = torch.as_tensor(mean, dtype=torch.float64).to(dtype=dt, device=dev).view(1, C, 1, 1)
+    s = torch.as_tensor(std, dtype=torch.float64).to(dtype=dt, device=dev).view(1, C, 1, 1)
+    ux, uy = x * s + m, y.to(dt) * s + m
+    L = float(data_range)
+    win = gaussian_window(dt, dev)
+    c1, c2 = (0.01 * L) ** 2, (0.03 * L) ** 2
+    mx, my = windowed(ux, win), windowed(uy, win)
+    sxx = windowed(ux * ux, win) - mx * mx
+    syy = windowed(uy * uy, win) - my * my
+    sxy = windowed(ux * uy, win) - mx * my
+    A1, A2, B1, B2 = 2 * mx * my + c1, 2 * sxy + c2, mx * mx + my * my + c1, sxx + syy + c2
+    S = A1 * A2 / (B1 * B2)
+    dA1, dA2, dB1, dB2 = A2 / (B1 * B2), A1 / (B1 * B2), -S / B1, -S / B2
+    alpha = 2 * my * (dA1 - dA2) + 2 * mx * (dB1 - dB2)
+    beta, gamma = 2 * dB2, 2 * dA2
+
+    def transposed(z):
+        n = win.numel()
+        v = z.new_zeros(*z.shape[:-2], H, z.shape[-1])
+        for k in range(n):
+            v[..., k:k + H - n + 1, :] += win[k] * z
+        h = z.new_zeros(*z.shape[:-2], H, W)
+        for k in range(n):
+            h[..., :, k:k + W - n + 1] += win[k] * v
+        return h
+
+    g = transposed(alpha) + ux * transposed(beta) + uy * transposed(gamma)
+    return g * (-lam / (F_ * C * (H - WINDOW + 1) * (W - WINDOW + 1))) * s

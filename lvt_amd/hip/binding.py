@@ -185,6 +185,8 @@ def _declare(lib):
         "lvt_mse_bwd": (ci, [vp, vp, cll, C.c_double, cf, vp, vp, ci, vp, vp, vp]),
         "lvt_l1_fwd": (ci, [vp, vp, cll, C.c_double, cf, vp, vp, sz, vp]),
         "lvt_l1_bwd": (ci, [vp, vp, cll, C.c_double, cf, vp, vp, ci, vp, vp, vp]),
+        "lvt_mse_bwd_plus": (ci, [vp, vp, cll, C.c_double, cf, vp, vp, vp, vp, vp, vp]),
+        "lvt_l1_bwd_plus": (ci, [vp, vp, cll, C.c_double, cf, vp, vp, vp, vp, vp, vp]),
         "lvt_tanh_bwd": (ci, [vp, vp, cll, vp, vp, vp]),
         "lvt_sigmoid_bwd": (ci, [vp, vp, cll, vp, vp, vp]),
         "lvt_axpy": (ci, [vp, vp, cll, vp, cf, vp, vp]),
@@ -243,6 +245,9 @@ def _declare(lib):
         "lvt_frame_quality_partials": (cll, [ci, ci, ci]),
         "lvt_frame_quality": (ci, [vp, vp, ci, ci, ci, ci, C.c_double, vp, cll, vp]),
         "lvt_frame_quality_finish": (ci, [vp, ci, ci, ci, ci, C.c_double, cll, vp, vp, vp]),
+        "lvt_ssim_loss_partials": (cll, [ci, ci, ci, ci]),
+        "lvt_ssim_loss_fwd": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, vp, C.c_double, C.c_double, vp, cll, vp, vp]),
+        "lvt_ssim_loss_finish": (ci, [vp, cll, ci, ci, ci, ci, C.c_double, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)

@@ -80,8 +80,68 @@ def frame_quality(a, b, data_range, acc=None, frames=None):
     return frames, acc
 
 
-def mse_bwd(a, b, denom, scale=1.0, gout=None, add=None, tanh_of_a=False, l1=False):
-    L.require(a, b, gout, add)
+def ssim_loss_fwd(xt, x, mean, std, data_range, lam, want_grad=False):
+    """The SSIM term of the reconstruction loss on channels-last activations (csrc/ssim_loss.hip; the rule:
+    lvt_amd.evaluation.quality.ssim_loss_reference).  xt (the reconstruction), x (the target): (N, 1, H, W, Cp) fp32 device
+    tensors, Cp = C rounded up to 4 with zero pad channels; mean, std: C float32 values each on the same device (tensors; a
+    sequence is copied there), the de-normalisation u = v * std[c] + mean[c].  -> (loss, G): loss the fp32 device scalar
+    lam * (1 - mean SSIM(u(xt), u(x))); G = d loss / d xt shaped like xt (pad channels exact 0) when `want_grad`, else None and
+    the backward half of the kernel is skipped (same loss bits).  Nothing is read on the host, and a refused call launches
+    nothing."""
+    if not torch.is_tensor(xt) or not torch.is_tensor(x):
+        raise L.LvtError("ssim_loss_fwd: tensors expected")
+    if tuple(xt.shape) != tuple(x.shape):
+        raise L.LvtError("ssim_loss_fwd: shapes differ, %s against %s" % (tuple(xt.shape), tuple(x.shape)))
+    if xt.dim() != 5 or xt.shape[1] != 1 or xt.numel() == 0 or xt.shape[-1] % 4:
+        raise L.LvtError("ssim_loss_fwd: frames are channels-last (N, 1, H, W, Cp) with Cp a multiple of 4, got %s" % (tuple(xt.shape),))
+    if xt.dtype != torch.float32 or x.dtype != torch.float32:
+        raise L.LvtError("ssim_loss_fwd: float32 frames only, got %s and %s" % (xt.dtype, x.dtype))
+    N, _, H, W, Cp = xt.shape
+    if H < 11 or W < 11:
+        raise L.LvtError("ssim_loss_fwd: H=%d W=%d, the 11x11 window needs H and W >= 11" % (H, W))
+    data_range, lam = float(data_range), float(lam)
+    if not 0.0 < data_range < float("inf"):
+        raise L.LvtError("ssim_loss_fwd: data_range must be positive and finite, got %r" % (data_range,))
+    if not 0.0 <= lam < float("inf"):
+        raise L.LvtError("ssim_loss_fwd: lam must be non-negative and finite, got %r" % (lam,))
+    Cc = len(mean)
+    if len(std) != Cc or Cc < 1 or (Cc + 3) // 4 * 4 != Cp:
+        raise L.LvtError("ssim_loss_fwd: %d means and %d stds for frames of %d channels (C rounded up to 4)" % (Cc, len(std), Cp))
+    L.require(xt, x)
+    if not torch.is_tensor(mean):
+        mean = torch.tensor([float(v) for v in mean], dtype=torch.float32, device=xt.device)
+    if not torch.is_tensor(std):
+        std = torch.tensor([float(v) for v in std], dtype=torch.float32, device=xt.device)
+    L.require(mean, std)
+    if mean.dtype != torch.float32 or std.dtype != torch.float32 or mean.dim() != 1 or std.dim() != 1:
+        raise L.LvtError("ssim_loss_fwd: mean and std are 1-D float32")
+    n = L.lib().lvt_ssim_loss_partials(N, H, W, Cp)
+    ws = L.workspace(n * 8, xt.device, "ssim_loss")
+    out = _f32(1, like=xt)
+    G = torch.empty_like(xt) if want_grad else None
+    L.check(L.lib().lvt_ssim_loss_fwd(L.ptr(xt), L.ptr(x), N, H, W, Cp, Cc, L.ptr(mean), L.ptr(std), data_range, lam, L.ptr(ws), n,
+                                      L.ptr(G), L.stream_ptr()), "lvt_ssim_loss_fwd")
+    L.check(L.lib().lvt_ssim_loss_finish(L.ptr(ws), n, N, H, W, Cc, lam, L.ptr(out), L.stream_ptr()), "lvt_ssim_loss_finish")
+    return out.view(()), G
+
+
+def mse_bwd(a, b, denom, scale=1.0, gout=None, add=None, tanh_of_a=False, l1=False, g_plus=None, plus=None):
+    """`plus` (with `g_plus`): the gradient G of a second loss term w.r.t. `a` and the device scalar autograd hands back for that
+    term; the launch writes gout c (a - b | sign) + g_plus G as ONE tensor and reports its max |.| (lvt_mse_bwd_plus /
+    lvt_l1_bwd_plus)."""
+    L.require(a, b, gout, add, g_plus, plus)
+    if (plus is None) != (g_plus is None):
+        raise L.LvtError("mse_bwd: plus and g_plus go together")
+    if plus is not None:
+        if add is not None or tanh_of_a:
+            raise L.LvtError("mse_bwd: plus excludes add and tanh_of_a")
+        if tuple(plus.shape) != tuple(a.shape) or plus.dtype != torch.float32 or g_plus.numel() != 1 or g_plus.dtype != torch.float32:
+            raise L.LvtError("mse_bwd: plus is shaped like a, g_plus one float32 value")
+        out = torch.empty_like(a)
+        L.check((L.lib().lvt_l1_bwd_plus if l1 else L.lib().lvt_mse_bwd_plus)(
+            L.ptr(a), L.ptr(b), a.numel(), float(denom), scale, L.ptr(gout), L.ptr(g_plus), L.ptr(plus), L.ptr(out), L.out_amax(out),
+            L.stream_ptr()), "lvt_mse_bwd_plus")
+        return out
     out = torch.empty_like(a)
     L.check((L.lib().lvt_l1_bwd if l1 else L.lib().lvt_mse_bwd)(L.ptr(a), L.ptr(b), a.numel(), float(denom), scale, L.ptr(gout), L.ptr(add),
                                 1 if tanh_of_a else 0, L.ptr(out), L.out_amax(out), L.stream_ptr()), "lvt_mse_bwd")

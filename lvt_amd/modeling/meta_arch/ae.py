@@ -17,7 +17,7 @@ from ...utils.events import get_event_storage
 from .. import convstack
 from ..encoder import build_encoder
 from ..generator import build_generator
-from ..loss.loss import mse
+from ..loss import ReconstructionLoss
 from .build import META_ARCH_REGISTRY
 from .common import init_weights, stack_to_device
 
@@ -40,6 +40,7 @@ class AutoEncoderModel(nn.Module):
         self.normalizer = lambda x: (x - self._pixel_mean.view(1, c, 1, 1)) / self._pixel_std.view(1, c, 1, 1)
         self.back_normalizer = lambda y: y * self._pixel_std.view(1, c, 1, 1) + self._pixel_mean.view(1, c, 1, 1)
         self.vis_period = cfg.VIS_PERIOD
+        self.reconstruction_loss = ReconstructionLoss(cfg, pixel=False)      # plain mse (+ the SSIM term, LOSS.SSIM.LAMBDA)
         self._reducers = []
         self.to(self.device)
 
@@ -161,7 +162,7 @@ class AutoEncoderModel(nn.Module):
     def _generator_loss_cl(self, x):
         out = self.generator.forward_cl(self.encoder.forward_cl(x))
         c = len(self.cfg.MODEL.PIXEL_MEAN)
-        return {"loss_ae_mse": mse(out, x, denom=x.numel() // x.shape[-1] * c)}
+        return self.reconstruction_loss(out, x, denom=x.numel() // x.shape[-1] * c, key="loss_ae_mse")
 
     def _supervised_loss_cl(self, x):
         return self._generator_loss_cl(x)

@@ -8,7 +8,7 @@ import os
 
 from ...solver import build_lr_scheduler, build_optimizer
 from ...utils.checkpoint import Checkpointer
-from ..loss import PixelLoss
+from ..loss import ReconstructionLoss
 from ..loss.loss import mse
 from ..vq import DVQEmbedding, SingleVQEmbedding
 from .ae import AutoEncoderModel
@@ -30,7 +30,8 @@ class VQVAEModel(AutoEncoderModel):
         if cb.RESTART.ENABLED:
             # (the un-offset config seed: every rank must draw the same rows)
             self.codebook.enable_restart(cb.RESTART.THRESHOLD, max(cfg.SEED, 0))
-        self.pixel_loss = PixelLoss(cfg)
+        self.reconstruction_loss = ReconstructionLoss(cfg)      # PixelLoss's choice (+ LOSS.SSIM.LAMBDA * (1 - SSIM))
+        self.pixel_loss = self.reconstruction_loss.pixel_loss
         self.beta = cb.BETA
         self.to(self.device)
 
@@ -96,10 +97,8 @@ class VQVAEModel(AutoEncoderModel):
             raise
         z_q_bar = self.codebook.finish_ema()
         c = len(self.cfg.MODEL.PIXEL_MEAN)
-        loss = {
-            "loss_reconstruction": self.pixel_loss(x_tilde, x, denom=x.numel() // x.shape[-1] * c),
-            "loss_commitment": mse(z_e, z_q_bar.detach(), scale=self.beta),
-        }
+        loss = self.reconstruction_loss(x_tilde, x, denom=x.numel() // x.shape[-1] * c)
+        loss["loss_commitment"] = mse(z_e, z_q_bar.detach(), scale=self.beta)
         if not self.use_codebook_ema:
             # vector-quantisation objective of a TRAINED codebook, under the reference's key (vqvae.py:83-84)
             loss["loss_dict"] = mse(z_q_bar, z_e.detach())
