@@ -402,7 +402,8 @@ int lvt_vq_ema_finalize_restart(const float *stats, const float *cand, int num, 
 
 /* ---- boundary layout conversion + input (de)normalisation (ae.py:32-37,151-168; K12) --------------
  * to_channels_last : in [B][C][R] -> out [B][R][ldo] (columns >= C zero); mode 1: (x - a[c]) / s[c]
- * to_channels_first: in [B][R][ldi] -> out [B][C][R];  mode 2: clamp(x * s[c] + a[c], lo, hi)          */
+ * to_channels_first: in [B][R][ldi] -> out [B][C][R];  mode 2: clamp(x * s[c] + a[c], lo, hi), a NaN stays a NaN (clamp_)
+ * mode 0 copies; each direction refuses the other's mode, and every other one, with LVT_EINVAL.            */
 int lvt_to_channels_last(const float *in, int B, int C, long long R, int ldo, int mode, const float *a,
                          const float *s, float *out, float *out_amax, void *stream);
 /* (out_amax, here and on lvt_mse_bwd / lvt_tanh_bwd: nullable, max |out| folded into a device scalar as lvt_amax_io.c is --

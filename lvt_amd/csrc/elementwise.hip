@@ -58,7 +58,12 @@ __global__ void lvt_to_channels_first_kernel(const float *__restrict__ in, int B
         const long long r = i % R; const long long t = i / R;
         const int c = t % C; const long long b = t / C;
         float v = in[(b * R + r) * ldi + c];
-        if (mode == 2) { v = v * s[c] + a[c]; v = fminf(fmaxf(v, lo), hi); }
+        if (mode == 2) {
+            // the comparisons keep a NaN pixel a NaN, as the reference's clamp_ does (fminf / fmaxf return the bound instead)
+            v = v * s[c] + a[c];
+            v = v < lo ? lo : v;
+            v = v > hi ? hi : v;
+        }
         out[i] = v;
     }
 }
@@ -66,6 +71,7 @@ __global__ void lvt_to_channels_first_kernel(const float *__restrict__ in, int B
 extern "C" int lvt_to_channels_last(const float *in, int B, int C, long long R, int ldo, int mode, const float *a,
                                     const float *s, float *out, float *out_amax, void *stream) {
     LVT_REQUIRE(in && out && B > 0 && C > 0 && R > 0 && ldo >= C, "to_channels_last: bad args");
+    LVT_REQUIRE(mode == 0 || mode == 1, "to_channels_last: mode %d (0: copy, 1: (x - a) / s)", mode);
     LVT_REQUIRE(mode == 0 || (a && s), "to_channels_last: affine tables missing");
     hipLaunchKernelGGL(lvt_to_channels_last_kernel, dim3(grid_for((long long)B * R * ldo, 256, out_amax ? 2048 : 8192)), dim3(256), 0,
                        (hipStream_t)stream, in, B, C, R, ldo, mode, a, s, out, out_amax);
@@ -75,6 +81,7 @@ extern "C" int lvt_to_channels_last(const float *in, int B, int C, long long R, 
 extern "C" int lvt_to_channels_first(const float *in, int B, int C, long long R, int ldi, int mode, const float *a,
                                      const float *s, float lo, float hi, float *out, void *stream) {
     LVT_REQUIRE(in && out && B > 0 && C > 0 && R > 0 && ldi >= C, "to_channels_first: bad args");
+    LVT_REQUIRE(mode == 0 || mode == 2, "to_channels_first: mode %d (0: copy, 2: clamp(x * s + a))", mode);
     LVT_REQUIRE(mode == 0 || (a && s), "to_channels_first: affine tables missing");
     hipLaunchKernelGGL(lvt_to_channels_first_kernel, dim3(grid_for((long long)B * C * R, 256)), dim3(256), 0,
                        (hipStream_t)stream, in, B, C, R, ldi, mode, a, s, lo, hi, out);
