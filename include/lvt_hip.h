@@ -805,6 +805,21 @@ int lvt_ssim_loss_fwd(const float *xt, const float *x, int N, int H, int W, int 
 int lvt_ssim_loss_finish(const double *partials, long long n_partials, int N, int H, int W, int C, double lam, float *out,
                          void *stream);
 
+/* ---- residual dropout of the video transformer (additive under ABI 680; csrc/dropout.hip; the rule in plain Python:
+ * lvt_amd/hip/dropout.py).  Element i of the flat tensor is kept iff word (i & 3) of Philox4x32-10 under the key
+ * (seed & 0xffffffff, seed >> 32) and the counter (g & 0xffffffff, g >> 32, site_rank, pass), g = i >> 2, is >= T;
+ * T = floor(p 2^32), s = fp32(1 / (1 - p)), both formed by the caller.
+ *   add: out[i] = keep ? res[i] + z[i] * s : res[i]; with res == NULL: keep ? z[i] * s : +0.  The product is rounded on its own
+ *        (no FMA).  out may be z itself.
+ *   bwd: out[i] = keep ? g[i] * s : +0 -- the add without res, under the same (seed, site_rank, pass, T, s).
+ * Any n >= 1 (the unused words of a partial last group are discarded).  out_amax (nullable): integer atomic max of the bit
+ * pattern of max |out| over its finite elements, as on the other helper kernels.  n <= 0, a null z / g / out, a pointer that is
+ * not 16-byte aligned: LVT_EINVAL before any device work.  The same arguments give the same bits. */
+int lvt_dropout_add(const float *z, const float *res, long long n, unsigned long long seed, unsigned site_rank, unsigned pass,
+                    unsigned T, float s, float *out, unsigned *out_amax, void *stream);
+int lvt_dropout_bwd(const float *g, long long n, unsigned long long seed, unsigned site_rank, unsigned pass, unsigned T, float s,
+                    float *out, unsigned *out_amax, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@ _TABLE = [
     ('MODEL.AUTOREGRESSIVE.VT.SHARE_P', True),
     ('MODEL.AUTOREGRESSIVE.VT.SHARE_EMBEDDINGS', False),
     ('MODEL.AUTOREGRESSIVE.VT.CLASS_NUM', 0),
+    ('MODEL.AUTOREGRESSIVE.VT.DROPOUT', 0.0),        # residual dropout of every attention layer's two branches; 0.0: off
     ('MODEL.ENCODER.WEIGHTS', ''),
     ('MODEL.ENCODER.NAME', ''),
     ('MODEL.ENCODER.IN_CHANNELS', 1),

@@ -248,6 +248,8 @@ def _declare(lib):
         "lvt_ssim_loss_partials": (cll, [ci, ci, ci, ci]),
         "lvt_ssim_loss_fwd": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, vp, C.c_double, C.c_double, vp, cll, vp, vp]),
         "lvt_ssim_loss_finish": (ci, [vp, cll, ci, ci, ci, ci, C.c_double, vp, vp]),
+        "lvt_dropout_add": (ci, [vp, vp, cll, C.c_ulonglong, C.c_uint, C.c_uint, C.c_uint, cf, vp, vp, vp]),
+        "lvt_dropout_bwd": (ci, [vp, cll, C.c_ulonglong, C.c_uint, C.c_uint, C.c_uint, cf, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)

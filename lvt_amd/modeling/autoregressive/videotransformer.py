@@ -17,10 +17,18 @@ from torch import nn
 from ...hip import binding as L
 from ...hip import ew, tx
 from ...hip import gemm as G
+from ...hip.dropout import DropoutState, check_rate
 from .. import convstack
 from .autoregressive import Autoregressive
 from .build import AUTOREGRESSIVE_REGISTRY
 from .vt_attention import BlockLocalAttention, PositionalEncoding, linear_wgrad
+
+
+def _bind_dropout(layers, state, first):
+    """Residual dropout: the attention layers of a stack share one stream and are numbered from `first`."""
+    for i, layer in enumerate(layers):
+        layer.bind_dropout(state, first + i)
+    return first + len(layers)
 
 
 class MaskedConv3d(nn.Module):
@@ -126,14 +134,15 @@ class _EncoderFrontFn(torch.autograd.Function):
 
 
 class VTEncoder(nn.Module):
-    def __init__(self, nc, nv, da, de, d, blocks, n_heads, kernel_size, stride, pad_value=-1, class_num=0):
+    def __init__(self, nc, nv, da, de, d, blocks, n_heads, kernel_size, stride, pad_value=-1, class_num=0, dropout=0.0):
         super().__init__()
         self.nc, self.nv, self.stride, self.pad_value, self.class_num = nc, nv, tuple(stride), pad_value, class_num
         self.kernel_size = tuple(kernel_size)
         self.conv = nn.Conv3d(nc * nv, de, kernel_size, stride, bias=True)
         self.positional_encoder = PositionalEncoding(de)      # constructed but never applied (reference quirk)
-        self.block_local_attention = nn.Sequential(*[BlockLocalAttention(blk, da, d, nh, masked=False)
+        self.block_local_attention = nn.Sequential(*[BlockLocalAttention(blk, da, d, nh, masked=False, dropout=dropout)
                                                      for blk, nh in zip(blocks, n_heads)])
+        _bind_dropout(self.block_local_attention, DropoutState(), 0)
         st, sh, sw = stride
         self.slice_embedding = nn.Embedding(st * sh * sw, de)
         if class_num > 0:
@@ -223,15 +232,16 @@ class _DecoderFrontFn(torch.autograd.Function):
 
 
 class VTDecoder(nn.Module):
-    def __init__(self, nc, nv, da, de, d, blocks, n_heads):
+    def __init__(self, nc, nv, da, de, d, blocks, n_heads, dropout=0.0):
         super().__init__()
         self.ch_embedder = nn.ModuleList([nn.Embedding(nv, de) for _ in range(nc)])
         self.de, self.nc, self.nv = de, nc, nv
         self.conv = MaskedConv3d(de, d, (3, 3, 3))
         self.positional_encoder = PositionalEncoding(d)
         self.linear_projector = nn.Conv3d(d, d, 1, bias=False)
-        self.block_local_attention = nn.Sequential(*[BlockLocalAttention(blk, da, d, nh, masked=True)
+        self.block_local_attention = nn.Sequential(*[BlockLocalAttention(blk, da, d, nh, masked=True, dropout=dropout)
                                                      for blk, nh in zip(blocks, n_heads)])
+        _bind_dropout(self.block_local_attention, DropoutState(), 0)
 
     def forward_tokens(self, sl, zl_tok):
         b, nc, t, h, w = sl.shape
@@ -483,20 +493,36 @@ class VideoTransformer(Autoregressive):
         return cls(nc=v.NC, nv=v.NV, kernel_size=v.KERNEL, stride=v.STRIDE, d=v.D, da=v.DA, de=v.DE,
                    blocks_e=v.BLOCKS_E, n_head_e=v.N_HEAD_E, blocks_d=v.BLOCKS_D, n_head_d=v.N_HEAD_D,
                    pad_value=v.PAD_VALUE, share_p=v.SHARE_P, share_embeddings=v.SHARE_EMBEDDINGS,
-                   class_num=v.CLASS_NUM)
+                   class_num=v.CLASS_NUM, dropout=v.DROPOUT)
 
     def __init__(self, nc, nv, da, de, d, blocks_e, n_head_e, kernel_size, stride, blocks_d, n_head_d, pad_value,
-                 share_p, share_embeddings, class_num):
+                 share_p, share_embeddings, class_num, dropout=0.0):
         super().__init__()
         self.nv, self.nc = nv, nc
-        self.encoder = VTEncoder(nc, nv, da, de, d, blocks_e, n_head_e, kernel_size, stride, pad_value, class_num)
-        self.decoder = VTDecoder(nc, nv, da, de, d, blocks_d, n_head_d)
+        self.dropout = check_rate(dropout)                 # (ValueError that names the config key, GPU or not)
+        self.encoder = VTEncoder(nc, nv, da, de, d, blocks_e, n_head_e, kernel_size, stride, pad_value, class_num, self.dropout)
+        self.decoder = VTDecoder(nc, nv, da, de, d, blocks_d, n_head_d, self.dropout)
         self.ch_predictor = ChannelPredictor(d, nc, nv, de, share_p=share_p, share_embeddings=share_embeddings)
         if share_embeddings:
             self.ch_predictor.tie_embeddings(self.decoder.ch_embedder)       # (videotransformer.py:236, 245)
+        # one dropout stream for the model; its layers count the encoder's first, then the decoder's (site = 2 layer + branch)
+        self.dropout_state = DropoutState()
+        n = _bind_dropout(self.encoder.block_local_attention, self.dropout_state, 0)
+        _bind_dropout(self.decoder.block_local_attention, self.dropout_state, n)
+
+    def set_dropout_seed(self, seed):
+        """Replace the stream's 64-bit seed (torch.initial_seed() at construction)."""
+        self.dropout_state.set_seed(seed)
+
+    def begin_dropout_pass(self):
+        """Advance the stream's pass index: once per training-mode forward, and only at a rate > 0 (the first pass uses 0)."""
+        if self.training and self.dropout > 0.0:
+            self.dropout_state.begin_pass()
+        return self.dropout_state.pass_
 
     # token-major fast path used by VideoTransformerModel -----------------------------------------------
     def logits_tokens(self, context, slice, slice_idx, class_idx=None):
+        self.begin_dropout_pass()
         zl = self.encoder.forward_tokens(context, slice_idx, class_idx)
         yl = self.decoder.forward_tokens(slice, zl)
         return self.ch_predictor.logits_tokens(slice, yl)

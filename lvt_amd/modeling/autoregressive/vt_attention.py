@@ -15,6 +15,7 @@ from torch import nn
 from torch.nn import init
 
 from ...hip import binding as L
+from ...hip import dropout as D
 from ...hip import ew, tx
 from ...hip import gemm as G
 
@@ -219,7 +220,9 @@ def _use_planes(S, da, block, pairs):
 class _BlockLocalAttentionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, block, masked, dt, dh, dw, ln_w, ln_b, w_q, w_k, w_v, proj_w, f0w, f0b, f1w, f1b, f3w, f3b,
-                wqkv, p2=None):
+                wqkv, p2=None, drop=None):
+        # drop: None (eval mode, or rate 0: the launches of a layer without dropout, argument for argument) or (p, seed, site_rank,
+        # pass) of hip/dropout.py -- site_rank is the attention branch's, the FFN branch's the one after it
         L.require(x)
         M, d = x.shape
         S = block[0] * block[1] * block[2]
@@ -275,7 +278,13 @@ class _BlockLocalAttentionFn(torch.autograd.Function):
             G.gemm(P, v, o, S, da, S, ta=0, tb=1, lda=S, ldb=hd, ldc=hd, batch_outer=b, batch_inner=na,
                    sA=(na * S * S, S * S), sB=(S * hd, da), sC=(S * hd, da))
         y1 = torch.empty(M, d, dtype=torch.float32, device=dev)
-        G.gemm(o, proj_w, y1, M, d, hd, flags=L.EPI_RESIDUAL, res=x)
+        if drop is None:
+            G.gemm(o, proj_w, y1, M, d, hd, flags=L.EPI_RESIDUAL, res=x)
+        else:
+            # y1 = x + D1(o proj^T): the branch leaves its GEMM without the residual and is dropped in place before the add
+            p_drop, seed, site, pass_ = drop
+            G.gemm(o, proj_w, y1, M, d, hd)
+            D.dropout_add(y1, x, (seed, site, pass_), p_drop, inplace=True)
         h1 = torch.empty(M, f1w.shape[0], dtype=torch.float32, device=dev)
         if p2_full:
             fn, fn_img, mean2, rstd2 = ew.layernorm_fwd_p2(y1, f0w, f0b)
@@ -287,10 +296,15 @@ class _BlockLocalAttentionFn(torch.autograd.Function):
         if L.RELU_TRACE is not None:
             L.RELU_TRACE.append(h1 > 0)
         y2 = torch.empty(M, d, dtype=torch.float32, device=dev)
-        G.gemm(h1, f3w, y2, M, d, f3w.shape[1], flags=L.EPI_BIAS | L.EPI_RESIDUAL, bias=f3b, res=y1)
+        if drop is None:
+            G.gemm(h1, f3w, y2, M, d, f3w.shape[1], flags=L.EPI_BIAS | L.EPI_RESIDUAL, bias=f3b, res=y1)
+        else:
+            G.gemm(h1, f3w, y2, M, d, f3w.shape[1], flags=L.EPI_BIAS, bias=f3b)
+            D.dropout_add(y2, y1, (seed, site + 1, pass_), p_drop, inplace=True)
         ctx.save_for_backward(x, mean1, rstd1, xn, qkv, P, o, y1, mean2, rstd2, fn, h1,
                               ln_w, wqkv, proj_w, f0w, f1w, f3w, dt, dh, dw)
         ctx.block, ctx.dims, ctx.masked, ctx.planes, ctx.flash = block, (M, d, S, b, na, da), bool(masked), bool(planes), bool(flash)
+        ctx.drop = drop              # the backward regenerates both masks from these four numbers: nothing mask-sized is saved
         return y2
 
     @staticmethod
@@ -303,31 +317,37 @@ class _BlockLocalAttentionFn(torch.autograd.Function):
         dev = x.device
         dy2 = dy2.contiguous()
         dff = f1w.shape[0]
-        # FFN: y2 = h1 W3^T + b3 + y1 ; h1 = relu(fn W1^T + b1)
+        # FFN: y2 = D2(h1 W3^T + b3) + y1 ; h1 = relu(fn W1^T + b1).  dz2 / dz1: the gradients of the two branches behind their
+        # dropout (dy2 / dy1 themselves without one); the residual paths (the `add=` of the LayerNorm backwards) keep dy2 / dy1
+        drop = ctx.drop
+        dz2 = dy2 if drop is None else D.dropout_bwd(dy2, (drop[1], drop[2] + 1, drop[3]), drop[0])
         dh1 = torch.empty(M, dff, dtype=torch.float32, device=dev)
-        G.gemm(dy2, f3w, dh1, M, dff, d, ta=0, tb=1, ldb=dff, flags=L.EPI_MASK, mask=h1)
+        G.gemm(dz2, f3w, dh1, M, dff, d, ta=0, tb=1, ldb=dff, flags=L.EPI_MASK, mask=h1)
         dfn = torch.empty(M, d, dtype=torch.float32, device=dev)
         G.gemm(dh1, f1w, dfn, M, d, dff, ta=0, tb=1, ldb=d)
         if d == dff:
             # both FFN weight gradients are (d x d) = dy^T x products over the same rows: one launch
-            dwp, dbp = linear_wgrad_pair(dy2, h1, dh1, fn, d, dff, M)
+            dwp, dbp = linear_wgrad_pair(dz2, h1, dh1, fn, d, dff, M)
             df3w, df3b, df1w, df1b = dwp[0], dbp[0], dwp[1], dbp[1]
         else:
-            df3w, df3b = linear_wgrad(dy2, h1, d, dff, M, want_bias=True)
+            df3w, df3b = linear_wgrad(dz2, h1, d, dff, M, want_bias=True)
             df1w, df1b = linear_wgrad(dh1, fn, dff, d, M, want_bias=True)
         dy1, df0w, df0b = ew.layernorm_bwd(dfn, y1, mean2, rstd2, f0w, add=dy2)
-        # proj: y1 = o proj^T + x
+        del dz2
+        # proj: y1 = D1(o proj^T) + x
+        dz1 = dy1 if drop is None else D.dropout_bwd(dy1, (drop[1], drop[2], drop[3]), drop[0])
         if ctx.planes:
             # dO leaves its GEMM as bf16x3 planes; the whole attention core backward is lvt_attn_bwd_planes
             do = torch.empty(3, M, hd, dtype=torch.bfloat16, device=dev)
-            G.gemm(dy1, proj_w, do, M, hd, d, ta=0, tb=1, ldb=hd, flags=L.EPI_PLANES, c_plane=M * hd)
-            dproj = linear_wgrad(dy1, o, d, hd, M)
+            G.gemm(dz1, proj_w, do, M, hd, d, ta=0, tb=1, ldb=hd, flags=L.EPI_PLANES, c_plane=M * hd)
+            dproj = linear_wgrad(dz1, o, d, hd, M)
             dqkv, ddt, ddh, ddw = tx.attn_bwd_planes(qkv, do, P, o, b, na, S, da, temper, ctx.block, ctx.masked)
             return _BlockLocalAttentionFn._finish_backward(ctx, dqkv, ddt, ddh, ddw, dy1, dproj, df0w, df0b, df1w, df1b,
                                                             df3w, df3b)
         do = torch.empty(M, hd, dtype=torch.float32, device=dev)
-        G.gemm(dy1, proj_w, do, M, hd, d, ta=0, tb=1, ldb=hd)
-        dproj = linear_wgrad(dy1, o, d, hd, M)
+        G.gemm(dz1, proj_w, do, M, hd, d, ta=0, tb=1, ldb=hd)
+        dproj = linear_wgrad(dz1, o, d, hd, M)
+        del dz1
         if ctx.flash:
             # the whole attention core backward on fp32 operands: P and dS are recomputed from q, k, v, dO and the row statistics.
             # `o` selects the one-pass form of the query-stationary launch (delta = dO . O + the row correction): -72 us per
@@ -374,14 +394,18 @@ class _BlockLocalAttentionFn(torch.autograd.Function):
                sB=(M * hd, da), sC=(na * d * da, d * da), splits=_splits(3 * na * -(-d // 128), M))
         dx, dlnw, dlnb = ew.layernorm_bwd(dxn, x, mean1, rstd1, ln_w, add=dy1)
         return (dx, None, None, ddt, ddh, ddw, dlnw, dlnb, dws[0], dws[1], dws[2], dproj, df0w, df0b,
-                df1w, df1b, df3w, df3b, None, None)
+                df1w, df1b, df3w, df3b, None, None, None)
 
 
 class BlockLocalAttention(nn.Module):
-    def __init__(self, block_size, da, d, n_head, masked=False):
+    def __init__(self, block_size, da, d, n_head, masked=False, dropout=0.0):
         super().__init__()
         self.block_size = tuple(block_size)
         self.n_head, self.masked = n_head, masked
+        # residual dropout: plain attributes, no parameters or buffers.  A layer built on its own is layer 0 of a
+        # stream of its own; VideoTransformer numbers its layers and hands them its state (bind_dropout)
+        self.dropout = D.check_rate(dropout)
+        self.bind_dropout(D.DropoutState(), 0)
         self.mha = MultiHeadAttention(n_head, d, da)
         self.ffn = nn.Sequential(nn.LayerNorm(d), nn.Linear(d, d), nn.ReLU(True), nn.Linear(d, d))
         t, h, w = self.block_size
@@ -408,6 +432,18 @@ class BlockLocalAttention(nn.Module):
         return (self.dt_bank.index_select(1, self.dt) + self.dh_bank.index_select(1, self.dh)
                 + self.dw_bank.index_select(1, self.dw)).view(self.n_head, 1, s, s)
 
+    def bind_dropout(self, state, layer):
+        """The stream this layer draws from (hip/dropout.py DropoutState) and its number among the model's attention layers."""
+        D.site_rank(layer, 1)                    # more than 2048 layers: ValueError
+        self._dropout_state, self.dropout_layer = state, layer      # (plain attributes: no state_dict entry)
+
+    def _drop_args(self):
+        """None in eval mode or at rate 0, else (p, seed, site_rank of the attention branch, pass)."""
+        if not (self.dropout > 0.0 and self.training):
+            return None
+        st = self._dropout_state
+        return (self.dropout, st.seed, D.site_rank(self.dropout_layer, 0, D.current_rank()), st.pass_)
+
     def forward_tokens(self, x_tok, thw=None):
         """(b*T*H*W, d) token-major -> same.  thw = (T, H, W) of the incoming volume; when it differs from the
         block size the tokens are regrouped block by block (vt_attention.py:189-200)."""
@@ -420,7 +456,8 @@ class BlockLocalAttention(nn.Module):
         y = _BlockLocalAttentionFn.apply(
             x_tok, self.block_size, self.masked, self.dt_bank, self.dh_bank, self.dw_bank,
             m.layer_norm.weight, m.layer_norm.bias, m.w_q, m.w_k, m.w_v, m.proj.weight,
-            f[0].weight, f[0].bias, f[1].weight, f[1].bias, f[3].weight, f[3].bias, m.packed_qkv(), getattr(self, "_p2", None))
+            f[0].weight, f[0].bias, f[1].weight, f[1].bias, f[3].weight, f[3].bias, m.packed_qkv(), getattr(self, "_p2", None),
+            self._drop_args())
         if split:
             y = _RowPermuteFn.apply(y, inv, perm, S)
         return y
