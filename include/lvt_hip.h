@@ -786,6 +786,27 @@ int lvt_frame_quality(const float *a, const float *b, int F, int C, int H, int W
 int lvt_frame_quality_finish(const double *partials, int F, int C, int H, int W, double data_range, long long n_partials,
                              double *frames, double *acc, void *stream);
 
+/* ---- best-of-N quality of sampled videos (additive under ABI 680; csrc/quality.hip; the rule in plain torch:
+ * lvt_amd/evaluation/quality.py prediction_quality_reference).
+ *   lvt_frame_quality_vs: lvt_frame_quality with frame f of a (F frames) compared against frame f % Fb of b (Fb frames): S sampled
+ *      videos of T frames against ONE target of T frames are F = S T, Fb = T, and no copy of the target is made.  The same kernel,
+ *      tiling and partials layout, for the same lvt_frame_quality_finish; with Fb == F the bits of lvt_frame_quality.  Its
+ *      refusals, and F % Fb != 0 or Fb < 1: LVT_EINVAL before any device work.
+ *   lvt_prediction_select: one workgroup over frames, the S * T pairs {psnr, ssim} lvt_frame_quality_finish wrote, sample-major
+ *      (frames[2 (s T + t)]).  The score of sample s under a metric is the fp64 sum of its values over t = n_prime .. T-1 in
+ *      ascending t, divided by T - n_prime (a +inf psnr takes part).  best[0] / best[1] = the sample with the largest psnr / ssim
+ *      score; equal scores resolve to the lowest index; a NaN score loses against every other, and sample 0 is chosen when all are
+ *      NaN.  curves: T * 8 doubles the caller owns and zeroes, this launch its only writer; for t >= n_prime (rows below stay
+ *      untouched) curves[8 t + k] +=
+ *        0: psnr[best[0], t] if finite, else 0     1: 1 if it is finite, else 0     2: ssim[best[1], t]
+ *        3: sum over s of the finite psnr[s, t]    4: their number                  5: sum over s of ssim[s, t]
+ *        6: 1 (clips)                              7: S (sampled videos)
+ *      with the sums over s in ascending s.  No atomics: the same inputs give the same bits.  best: 2 ints, overwritten.  A null
+ *      or misaligned pointer, S < 1, T < 1, n_prime outside [0, T): LVT_EINVAL before any device work. */
+int lvt_frame_quality_vs(const float *a, const float *b, int F, int Fb, int C, int H, int W, double data_range, double *partials,
+                         long long n_partials, void *stream);
+int lvt_prediction_select(const double *frames, int S, int T, int n_prime, double *curves, int *best, void *stream);
+
 /* ---- SSIM term of the reconstruction loss (additive under ABI 680; csrc/ssim_loss.hip; the rule in plain torch:
  * lvt_amd/evaluation/quality.py ssim_loss_reference).  xt, x: fp32 channels-last frames (N, 1, H, W, Cp), Cp = C rounded up to 4,
  * pad channels zero, 16-byte aligned, any H, W >= 11.  mean, stdv: C device floats; SSIM (the rule of lvt_frame_quality) is taken

@@ -11,6 +11,11 @@
 //                             the tile, sum of squared differences over the input pixels the tile OWNS), plain stores.
 //   lvt_frame_quality_finish  one workgroup: per frame the partials of its channels and tiles added in a fixed order -> frames[f] =
 //                             {psnr, ssim}, and the caller's accumulator {sum psnr, sum ssim, frames with mse != 0, frames}.
+// lvt_frame_quality_vs is the first launch with frame f of `a` compared against frame f % Fb of `b` (S sampled videos against
+// one target, PredictionQualityEvaluator): the same kernel, whose workgroups look up their plane of b.
+//   lvt_prediction_select     one workgroup over the (S, T) table `finish` wrote: the best sample per metric by the mean over the
+//                             predicted steps, and the clip's contribution to the per-step curves (the rule in plain Python:
+//                             prediction_quality_reference).
 // No atomics, fixed summation orders: the same inputs give the same bits.
 #include <math.h>
 #include "lvt_common.h"
@@ -39,8 +44,9 @@ __device__ __forceinline__ double fq_block_sum(double v, double *scratch) {
 }
 
 __global__ __launch_bounds__(FQ_THREADS) void lvt_frame_quality_kernel(const float *__restrict__ a, const float *__restrict__ b,
-                                                                       int H, int W, int tiles_x, int tiles, const FqWindow win,
-                                                                       double c1, double c2, double *__restrict__ partials) {
+                                                                       int C, int Fb, int H, int W, int tiles_x, int tiles,
+                                                                       const FqWindow win, double c1, double c2,
+                                                                       double *__restrict__ partials) {
     __shared__ float sa[FQ_IH][FQ_IW], sb[FQ_IH][FQ_IW];
     __shared__ float mid[5][FQ_IH][FQ_TW];
     __shared__ double scratch[4];
@@ -54,7 +60,10 @@ __global__ __launch_bounds__(FQ_THREADS) void lvt_frame_quality_kernel(const flo
     // the input pixels whose squared difference this tile counts: its own FQ_TH x FQ_TW block, and the last tile of a row /
     // column also takes the 10 rows / columns behind its map positions -- every pixel of the plane belongs to exactly one tile
     const int own_h = y0 + FQ_TH >= OH ? H - y0 : FQ_TH, own_w = x0 + FQ_TW >= OW ? W - x0 : FQ_TW;
-    const float *pa = a + plane * H * W, *pb = b + plane * H * W;
+    // frame f of a against frame f % Fb of b (Fb == F: plane against plane)
+    const long long fa = plane / C;
+    const long long plane_b = (fa % Fb) * C + (plane - fa * C);
+    const float *pa = a + plane * H * W, *pb = b + plane_b * H * W;
     const float piv_a = pa[(long long)y0 * W + x0], piv_b = pb[(long long)y0 * W + x0];
 
     double se = 0.0;
@@ -177,16 +186,17 @@ extern "C" long long lvt_frame_quality_partials(int C, int H, int W) {
     return (long long)C * lvt_cdiv(H - FQ_HALO, FQ_TH) * lvt_cdiv(W - FQ_HALO, FQ_TW);
 }
 
-extern "C" int lvt_frame_quality(const float *a, const float *b, int F, int C, int H, int W, double data_range, double *partials,
-                                 long long n_partials, void *stream) {
-    LVT_REQUIRE(a && b && partials, "frame_quality: null pointer");
-    LVT_REQUIRE((((uintptr_t)a | (uintptr_t)b) & 3) == 0 && lvt_aligned16(partials), "frame_quality: misaligned pointer");
-    LVT_REQUIRE(F > 0 && C > 0, "frame_quality: F=%d frames of C=%d channels", F, C);
-    LVT_REQUIRE(H >= FQ_WIN && W >= FQ_WIN, "frame_quality: H=%d W=%d, the 11x11 window needs H and W >= 11", H, W);
-    LVT_REQUIRE(fq_range_ok(data_range), "frame_quality: data_range must be positive and finite");
+static int fq_launch(const char *who, const float *a, const float *b, int F, int Fb, int C, int H, int W, double data_range,
+                     double *partials, long long n_partials, void *stream) {
+    LVT_REQUIRE(a && b && partials, "%s: null pointer", who);
+    LVT_REQUIRE((((uintptr_t)a | (uintptr_t)b) & 3) == 0 && lvt_aligned16(partials), "%s: misaligned pointer", who);
+    LVT_REQUIRE(F > 0 && C > 0, "%s: F=%d frames of C=%d channels", who, F, C);
+    LVT_REQUIRE(Fb > 0 && F % Fb == 0, "%s: F=%d frames against Fb=%d, F must be a multiple of Fb >= 1", who, F, Fb);
+    LVT_REQUIRE(H >= FQ_WIN && W >= FQ_WIN, "%s: H=%d W=%d, the 11x11 window needs H and W >= 11", who, H, W);
+    LVT_REQUIRE(fq_range_ok(data_range), "%s: data_range must be positive and finite", who);
     const long long need = lvt_frame_quality_partials(C, H, W);
-    LVT_REQUIRE(need == n_partials, "frame_quality: %lld partials per frame for a shape that needs %lld", n_partials, need);
-    LVT_REQUIRE((long long)F * need < (1ll << 31), "frame_quality: too many tiles in one launch");
+    LVT_REQUIRE(need == n_partials, "%s: %lld partials per frame for a shape that needs %lld", who, n_partials, need);
+    LVT_REQUIRE((long long)F * need < (1ll << 31), "%s: too many tiles in one launch", who);
     // the window: exp(-(k - 5)^2 / (2 sigma^2)), sigma 1.5, normalised in fp64, rounded once
     FqWindow win;
     double g[FQ_WIN], sum = 0.0;
@@ -194,10 +204,20 @@ extern "C" int lvt_frame_quality(const float *a, const float *b, int F, int C, i
     for (int k = 0; k < FQ_WIN; ++k) win.w[k] = (float)(g[k] / sum);
     const int tiles_x = (int)lvt_cdiv(W - FQ_HALO, FQ_TW), tiles = tiles_x * (int)lvt_cdiv(H - FQ_HALO, FQ_TH);
     const double c1 = (0.01 * data_range) * (0.01 * data_range), c2 = (0.03 * data_range) * (0.03 * data_range);
-    hipLaunchKernelGGL(lvt_frame_quality_kernel, dim3((unsigned)(F * need)), dim3(FQ_THREADS), 0, (hipStream_t)stream, a, b, H, W,
-                       tiles_x, tiles, win, c1, c2, partials);
+    hipLaunchKernelGGL(lvt_frame_quality_kernel, dim3((unsigned)(F * need)), dim3(FQ_THREADS), 0, (hipStream_t)stream, a, b, C, Fb,
+                       H, W, tiles_x, tiles, win, c1, c2, partials);
     LVT_CHECK_LAUNCH("lvt_frame_quality_kernel");
     return LVT_OK;
+}
+
+extern "C" int lvt_frame_quality(const float *a, const float *b, int F, int C, int H, int W, double data_range, double *partials,
+                                 long long n_partials, void *stream) {
+    return fq_launch("frame_quality", a, b, F, F, C, H, W, data_range, partials, n_partials, stream);
+}
+
+extern "C" int lvt_frame_quality_vs(const float *a, const float *b, int F, int Fb, int C, int H, int W, double data_range,
+                                    double *partials, long long n_partials, void *stream) {
+    return fq_launch("frame_quality_vs", a, b, F, Fb, C, H, W, data_range, partials, n_partials, stream);
 }
 
 extern "C" int lvt_frame_quality_finish(const double *partials, int F, int C, int H, int W, double data_range,
@@ -213,5 +233,107 @@ extern "C" int lvt_frame_quality_finish(const double *partials, int F, int C, in
     hipLaunchKernelGGL(lvt_frame_quality_finish_kernel, dim3(1), dim3(FQ_THREADS), 0, (hipStream_t)stream, partials, F, need,
                        (double)C * (H - FQ_HALO) * (W - FQ_HALO), (double)C * H * W, data_range * data_range, frames, acc);
     LVT_CHECK_LAUNCH("lvt_frame_quality_finish_kernel");
+    return LVT_OK;
+}
+
+// ---- best-of-N selection over the (S, T) table of {psnr, ssim} pairs (PredictionQualityEvaluator) -------------------
+// A candidate for the best sample: its score and its index.  `a` goes before `b` when its score is larger, when b's score is NaN
+// and a's is not, or when neither decides and a has the lower index: a total order, so the reduction below finds the same sample in
+// whatever order it meets them -- the largest score, the lowest index among equals, and sample 0 when every score is NaN.
+struct FqCand { double v; int s; };
+
+__device__ __forceinline__ bool fq_before(const FqCand &a, const FqCand &b) {
+    if (a.v > b.v) return true;
+    if (b.v > a.v) return false;
+    const bool na = a.v != a.v, nb = b.v != b.v;
+    if (na != nb) return nb;
+    return a.s < b.s;
+}
+
+// the first of the workgroup's 256 candidates in that order; every thread gets it.  `slots`: 4 candidates.
+__device__ __forceinline__ FqCand fq_block_best(FqCand c, FqCand *slots) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        FqCand o;
+        o.v = __shfl_xor(c.v, d, 64);
+        o.s = __shfl_xor(c.s, d, 64);
+        if (fq_before(o, c)) c = o;
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) slots[threadIdx.x >> 6] = c;
+    __syncthreads();
+    FqCand r = slots[0];
+#pragma unroll
+    for (int w = 1; w < FQ_THREADS / 64; ++w)
+        if (fq_before(slots[w], r)) r = slots[w];
+    return r;
+}
+
+__device__ __forceinline__ bool fq_finite(double v) { return v - v == 0.0; }         // (false for +-inf and NaN)
+
+// Thread i scores samples i, i + 256, ..: the plain fp64 sum of the sample's values over t = n_prime .. T-1 in ascending t, divided
+// by T - n_prime (a +inf psnr takes part).  After the two reductions thread j takes the steps n_prime + j, n_prime + j + 256, ..
+// and adds that step's row of eight values to `curves`, with the sums over the samples in ascending s.
+__global__ __launch_bounds__(FQ_THREADS) void lvt_prediction_select_kernel(const double *__restrict__ frames, int S, int T,
+                                                                           int n_prime, double *__restrict__ curves,
+                                                                           int *__restrict__ best) {
+    __shared__ FqCand slots[4];
+    const double steps = (double)(T - n_prime);
+    FqCand bp, bs;
+    bp.v = bs.v = (double)__builtin_nanf("");
+    bp.s = bs.s = 0x7fffffff;                               // a thread without a sample: behind every real candidate
+    for (int s = threadIdx.x; s < S; s += FQ_THREADS) {
+        const double *row = frames + 2 * (long long)s * T;
+        double p = 0.0, q = 0.0;
+        for (int t = n_prime; t < T; ++t) {
+            p += row[2 * t];
+            q += row[2 * t + 1];
+        }
+        FqCand cp, cs;
+        cp.v = p / steps; cp.s = s;
+        cs.v = q / steps; cs.s = s;
+        if (fq_before(cp, bp)) bp = cp;
+        if (fq_before(cs, bs)) bs = cs;
+    }
+    bp = fq_block_best(bp, slots);
+    bs = fq_block_best(bs, slots);
+    if (threadIdx.x == 0) {
+        best[0] = bp.s;
+        best[1] = bs.s;
+    }
+    for (int t = n_prime + threadIdx.x; t < T; t += FQ_THREADS) {
+        double ps = 0.0, pn = 0.0, sm = 0.0;
+        for (int s = 0; s < S; ++s) {
+            const double *v = frames + 2 * ((long long)s * T + t);
+            if (fq_finite(v[0])) {
+                ps += v[0];
+                pn += 1.0;
+            }
+            sm += v[1];
+        }
+        const double pb = frames[2 * ((long long)bp.s * T + t)];
+        double *c = curves + 8 * (long long)t;
+        if (fq_finite(pb)) {
+            c[0] += pb;
+            c[1] += 1.0;
+        }
+        c[2] += frames[2 * ((long long)bs.s * T + t) + 1];
+        c[3] += ps;
+        c[4] += pn;
+        c[5] += sm;
+        c[6] += 1.0;
+        c[7] += (double)S;
+    }
+}
+
+extern "C" int lvt_prediction_select(const double *frames, int S, int T, int n_prime, double *curves, int *best, void *stream) {
+    LVT_REQUIRE(frames && curves && best, "prediction_select: null pointer");
+    LVT_REQUIRE((((uintptr_t)frames | (uintptr_t)curves) & 7) == 0 && ((uintptr_t)best & 3) == 0,
+                "prediction_select: misaligned pointer");
+    LVT_REQUIRE(S >= 1 && T >= 1, "prediction_select: S=%d sampled videos of T=%d frames", S, T);
+    LVT_REQUIRE(n_prime >= 0 && n_prime < T, "prediction_select: n_prime=%d outside [0, T=%d)", n_prime, T);
+    hipLaunchKernelGGL(lvt_prediction_select_kernel, dim3(1), dim3(FQ_THREADS), 0, (hipStream_t)stream, frames, S, T, n_prime,
+                       curves, best);
+    LVT_CHECK_LAUNCH("lvt_prediction_select_kernel");
     return LVT_OK;
 }

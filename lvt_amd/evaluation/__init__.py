@@ -1,6 +1,7 @@
 from .evaluator import (BitsEvaluator, CodesExtractor, DatasetEvaluator, DatasetEvaluators, FrameQualityEvaluator, MSEEvaluator,
-                        VTSampler, build_evaluator, inference_on_dataset)
-from .quality import frame_quality_reference, ssim_loss_reference
+                        PredictionQualityEvaluator, VTSampler, build_evaluator, inference_on_dataset)
+from .quality import frame_quality_reference, prediction_quality_reference, ssim_loss_reference
 
 __all__ = ["BitsEvaluator", "CodesExtractor", "DatasetEvaluator", "DatasetEvaluators", "FrameQualityEvaluator", "MSEEvaluator",
-           "VTSampler", "build_evaluator", "frame_quality_reference", "inference_on_dataset", "ssim_loss_reference"]
+           "PredictionQualityEvaluator", "VTSampler", "build_evaluator", "frame_quality_reference", "inference_on_dataset",
+           "prediction_quality_reference", "ssim_loss_reference"]

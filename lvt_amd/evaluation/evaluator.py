@@ -2,6 +2,7 @@
 codes_extractor.py:36-53, mse_evaluation.py:28-47, bits_evaluation.py:28-58).  They only consume the
 dicts `model(inputs)` returns in inference mode; statistics are accumulated on the device and reduced across
 ranks with one all-reduce at the end (the reference gathers pickled python objects over gloo)."""
+import json
 import logging
 import math
 import os
@@ -15,7 +16,7 @@ import torch.nn.functional as F
 from ..data.latents import save_video_codes
 from ..layers import all_reduce_sum_
 from ..utils import comm
-from .quality import frame_quality_reference
+from .quality import frame_quality_reference, prediction_quality_reference
 
 
 class DatasetEvaluator:
@@ -198,6 +199,28 @@ class BitsEvaluator(_SumEvaluator):
         return results
 
 
+def build_sampler_vqvae(cfg, vqvae=None):
+    """The VQ-VAE named by cfg.TEST.VT_SAMPLER.VQ_VAE.* (or the one passed in), its weights loaded, frozen and in eval mode, as
+    vt_sampler.py:18-58 builds it -> (vqvae, INPUT.SCALE_TO_ZEROONE of its config).  An empty weight path keeps the initialised
+    weights, as fvcore's Checkpointer does."""
+    from ..config import get_cfg
+    from ..modeling import build_model
+    from ..utils.checkpoint import Checkpointer
+    vs = cfg.TEST.VT_SAMPLER.VQ_VAE
+    vq_cfg = get_cfg()
+    vq_cfg.merge_from_file(vs.CFG)
+    vq_cfg.MODEL.DEVICE = cfg.MODEL.DEVICE
+    vq_cfg.OUTPUT_DIR = cfg.OUTPUT_DIR
+    vqvae = vqvae if vqvae is not None else build_model(vq_cfg)
+    for module, path in ((vqvae.encoder, vs.ENCODER_WEIGHTS), (vqvae.generator, vs.GENERATOR_WEIGHTS),
+                         (vqvae.codebook, vs.CODEBOOK_WEIGHTS)):
+        if path:
+            Checkpointer(module).resume_or_load(path, resume=False)
+    vqvae.set_generator_requires_grad(False)
+    vqvae.eval()
+    return vqvae, vq_cfg.INPUT.SCALE_TO_ZEROONE
+
+
 class VTSampler(DatasetEvaluator):
     """Decodes and saves the videos `VideoTransformerModel` sampled in inference mode (reference:
     vidgen/evaluation/vt_sampler.py:18-81): builds the VQ-VAE named by cfg.TEST.VT_SAMPLER.VQ_VAE.*, and for every input writes
@@ -205,24 +228,9 @@ class VTSampler(DatasetEvaluator):
     (`vqvae.decode` -> gather + ResDecoder); an empty weight path keeps the initialised weights, as fvcore's Checkpointer does."""
 
     def __init__(self, cfg, dataset_name, distributed=True, output_dir=None, vqvae=None):
-        from ..config import get_cfg
-        from ..modeling import build_model
-        from ..utils.checkpoint import Checkpointer
         self._logger = logging.getLogger(__name__)
         self._dataset_name, self._distributed, self._output_dir = dataset_name, distributed, output_dir
-        vs = cfg.TEST.VT_SAMPLER.VQ_VAE
-        vq_cfg = get_cfg()
-        vq_cfg.merge_from_file(vs.CFG)
-        vq_cfg.MODEL.DEVICE = cfg.MODEL.DEVICE
-        vq_cfg.OUTPUT_DIR = cfg.OUTPUT_DIR
-        self.vqvae = vqvae if vqvae is not None else build_model(vq_cfg)
-        for module, path in ((self.vqvae.encoder, vs.ENCODER_WEIGHTS), (self.vqvae.generator, vs.GENERATOR_WEIGHTS),
-                             (self.vqvae.codebook, vs.CODEBOOK_WEIGHTS)):
-            if path:
-                Checkpointer(module).resume_or_load(path, resume=False)
-        self.vqvae.set_generator_requires_grad(False)
-        self.vqvae.eval()
-        self.scale_to_zeroone = vq_cfg.INPUT.SCALE_TO_ZEROONE
+        self.vqvae, self.scale_to_zeroone = build_sampler_vqvae(cfg, vqvae)
 
     @torch.no_grad()
     def process(self, inputs, outputs):
@@ -258,6 +266,110 @@ class VTSampler(DatasetEvaluator):
         return None
 
 
+class PredictionQualityEvaluator(DatasetEvaluator):
+    """Per-time-step PSNR and SSIM of the videos `VideoTransformerModel` sampled in inference mode, for the best of the
+    NUM_SAMPLES sampled futures of a clip and for their mean (the SVG / SAVP / SV2P protocol; the rule and the eight columns:
+    evaluation/quality.py prediction_quality_reference).  The target is the clip's own codes as the VQ-VAE renders
+    them (`decode_pixels(inp["image_sequence"])`: the mapper feeds codes, not pixels), the samples `decode_pixels` of
+    `out["samples"]`; the first TEST.VT_SAMPLER.N_PRIME frames are left out.  The best sample is chosen per metric by its mean
+    over the predicted steps.  Device frames go through `ew.prediction_quality` (csrc/quality.hip) into one (T, 8) device
+    accumulator, CPU frames through `prediction_quality_reference` into the same sums; nothing is read on the host before
+    `evaluate`.  A best frame that equals its target (mse == 0) has no finite PSNR: it is left out of the PSNR means and counted
+    as `identical_best_frames`.  The VQ-VAE is the one VTSampler builds (TEST.VT_SAMPLER.VQ_VAE.*)."""
+    DECODE_FRAMES = 512                       # frames per decode_pixels call
+
+    def __init__(self, cfg, dataset_name, distributed=True, output_dir=None, vqvae=None):
+        self._logger = logging.getLogger(__name__)
+        self._dataset_name, self._distributed, self._output_dir = dataset_name, distributed, output_dir
+        self.vqvae, scale_to_zeroone = build_sampler_vqvae(cfg, vqvae)
+        self._data_range = 1.0 if scale_to_zeroone else 255.0
+        self._n_prime = int(cfg.TEST.VT_SAMPLER.N_PRIME)
+        self.reset()
+
+    def reset(self):
+        self._acc = None                      # (T, 8) sums on the device of the first decoded clip
+
+    @staticmethod
+    def _frames_of(codes, time_first):
+        """Codes of one video as `decode_pixels` takes them: (T, nc, h, w), or (T, h, w) for a single codebook (as VTSampler)."""
+        codes = torch.as_tensor(codes)
+        if time_first:                        # the input clip: (T, nc, h, w)
+            return codes.squeeze(1) if codes.dim() == 4 and codes.shape[1] == 1 else codes
+        codes = codes.squeeze(0)              # a sample: (nc, T, h, w), or (1, T, h, w) -> (T, h, w)
+        return codes.transpose(0, 1).contiguous() if codes.dim() == 4 else codes
+
+    @torch.no_grad()
+    def process(self, inputs, outputs):
+        for inp, out in zip(inputs, outputs):
+            target = self.vqvae.decode_pixels(self._frames_of(inp["image_sequence"], True))
+            T = target.shape[0]
+            codes = torch.cat([self._frames_of(s, False) for s in out["samples"]])
+            S = codes.shape[0] // T
+            if S < 1 or codes.shape[0] != S * T:
+                raise ValueError("PredictionQualityEvaluator: %d sampled frames for a clip of %d" % (codes.shape[0], T))
+            samples = torch.cat([self.vqvae.decode_pixels(codes[i:i + self.DECODE_FRAMES])
+                                 for i in range(0, S * T, self.DECODE_FRAMES)]).view(S, *target.shape)
+            if self._acc is None:
+                self._acc = torch.zeros(T, 8, dtype=torch.float64, device=target.device)
+            elif self._acc.shape[0] != T:
+                raise ValueError("PredictionQualityEvaluator: a clip of %d frames after clips of %d" % (T, self._acc.shape[0]))
+            if target.is_cuda:
+                from ..hip import ew
+                ew.prediction_quality(samples.float().contiguous(), target.float().contiguous(), self._n_prime, self._data_range,
+                                      curves=self._acc)
+            else:
+                self._acc += prediction_quality_reference(samples, target, self._n_prime, self._data_range)[3]
+
+    def _agree_on_steps(self):
+        """T of this run.  A rank that saw no clip does not know it, and the all-reduce needs one shape everywhere: with more than
+        one rank, two integers (max T, -min T over the ranks that saw a clip) are agreed on first."""
+        T = -1 if self._acc is None else self._acc.shape[0]
+        dist_on = self._distributed and torch.distributed.is_available() and torch.distributed.is_initialized()
+        if not dist_on or comm.get_world_size() == 1:
+            return max(T, 0), "cpu" if self._acc is None else self._acc.device
+        dev = "cuda" if (torch.cuda.is_available() and torch.distributed.get_backend() == "nccl") else "cpu"
+        span = torch.tensor([T, -T if T >= 0 else -(1 << 30)], dtype=torch.int64, device=dev)
+        torch.distributed.all_reduce(span, op=torch.distributed.ReduceOp.MAX)
+        hi, lo = int(span[0]), -int(span[1])
+        if hi >= 0 and lo != hi:
+            raise ValueError("PredictionQualityEvaluator: clips of %d and of %d frames on different ranks" % (lo, hi))
+        return max(hi, 0), dev if self._acc is None else self._acc.device
+
+    def evaluate(self):
+        T, dev = self._agree_on_steps()
+        if self._acc is None:                 # a rank that saw no clip still takes part in the all-reduce
+            self._acc = torch.zeros(T, 8, dtype=torch.float64, device=dev)
+        acc = self._acc.clone()
+        if self._distributed:
+            all_reduce_sum_(acc)
+        if not comm.is_main_process():
+            return None
+        acc = acc.cpu()
+        n0 = min(self._n_prime, T)
+        rows = acc[n0:]
+
+        def ratio(num, den):
+            return float(num) / float(den) if float(den) > 0 else float("nan")
+
+        steps = list(range(n0, T))
+        per_frame = {"t": steps,
+                     "PSNR_best": [ratio(r[0], r[1]) for r in rows], "SSIM_best": [ratio(r[2], r[6]) for r in rows],
+                     "PSNR_mean": [ratio(r[3], r[4]) for r in rows], "SSIM_mean": [ratio(r[5], r[7]) for r in rows]}
+        tot = rows.sum(dim=0) if len(steps) else torch.zeros(8, dtype=torch.float64)
+        clips = int(rows[0, 6]) if len(steps) else 0
+        res = {"PSNR_best": ratio(tot[0], tot[1]), "SSIM_best": ratio(tot[2], tot[6]),
+               "PSNR_mean": ratio(tot[3], tot[4]), "SSIM_mean": ratio(tot[5], tot[7]), "per_frame": per_frame,
+               "clips": clips, "samples": int(rows[0, 7]) if len(steps) else 0, "n_prime": self._n_prime,
+               "identical_best_frames": int(tot[6] - tot[1]), "target": "decoded_codes"}
+        results = OrderedDict({"prediction_quality": res})
+        if self._output_dir:
+            os.makedirs(self._output_dir, exist_ok=True)
+            with open(os.path.join(self._output_dir, "prediction_quality_%s.json" % self._dataset_name), "w") as f:
+                json.dump(res, f, indent=1)
+        self._logger.info(results)
+        return results
+
+
 def build_evaluator(cfg, dataset_name, output_folder=None):
     """Substring dispatch on cfg.TEST.EVALUATORS like tools/train_net.py:35-57 of the reference."""
     if output_folder is None:
@@ -274,6 +386,8 @@ def build_evaluator(cfg, dataset_name, output_folder=None):
         evs.append(BitsEvaluator(dataset_name, True, output_folder))
     if "VTSampler" in cfg.TEST.EVALUATORS:
         evs.append(VTSampler(cfg, dataset_name, True, output_folder))
+    if "PredictionQualityEvaluator" in cfg.TEST.EVALUATORS:
+        evs.append(PredictionQualityEvaluator(cfg, dataset_name, True, output_folder))
     if not evs:
         raise NotImplementedError(cfg.TEST.EVALUATORS)
     return evs[0] if len(evs) == 1 else DatasetEvaluators(evs)

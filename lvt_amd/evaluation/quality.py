@@ -11,6 +11,10 @@ the data range; the SSIM of a frame is the mean of the map over all its channels
 
 PSNR of a frame is 10 log10(L^2 / mse) with the mse over all channels of the frame; a frame with mse == 0 has none (+inf).
 
+`prediction_quality_reference` states the best-of-N rule of `PredictionQualityEvaluator` on top of the per-frame values (which
+sample of S sampled videos is the best under each metric, and the eight per-step sums a clip contributes; csrc/quality.hip
+lvt_prediction_select).
+
 `ssim_loss_reference` states the SSIM term of the reconstruction loss (LOSS.SSIM.LAMBDA, csrc/ssim_loss.hip) with the
 same windows and constants, and `ssim_loss_closed_form` its gradient without autograd."""
 import math
@@ -69,6 +73,72 @@ def frame_quality_reference(a, b, data_range, dtype=torch.float64):
     sxy = windowed(x * y, win) - mx * my
     ssim = ((2 * (mx * my) + c1) * (2 * sxy + c2)) / ((mx * mx + my * my + c1) * (sxx + syy + c2))
     return psnr, ssim.mean(dim=(1, 2, 3))
+
+
+def best_sample(scores):
+    """The index of the largest of the 1-D `scores`: equal scores resolve to the lowest index, a NaN loses against every other
+    value, and index 0 is chosen when all are NaN."""
+    best = 0
+    for s in range(1, scores.numel()):
+        a, b = float(scores[s]), float(scores[best])
+        if a > b or (math.isnan(b) and not math.isnan(a)):
+            best = s
+    return best
+
+
+def prediction_select_reference(psnr, ssim, n_prime):
+    """The selection half of `prediction_quality_reference` on (S, T) tables of per-frame values -> (best (2,) int64, curves
+    (T, 8)): what lvt_prediction_select computes (csrc/quality.hip), in the same fp64 operations and orders."""
+    if psnr.dim() != 2 or tuple(psnr.shape) != tuple(ssim.shape) or psnr.shape[0] < 1 or psnr.shape[1] < 1:
+        raise ValueError("prediction quality: psnr and ssim are (S, T) with S, T >= 1, got %s and %s"
+                         % (tuple(psnr.shape), tuple(ssim.shape)))
+    S, T = psnr.shape
+    if not 0 <= n_prime < T:
+        raise ValueError("prediction quality: n_prime=%d outside [0, T=%d)" % (n_prime, T))
+    psnr, ssim = psnr.double(), ssim.double()
+    score_p, score_s = torch.zeros(S, dtype=torch.float64), torch.zeros(S, dtype=torch.float64)
+    for t in range(n_prime, T):                              # ascending t; inf + finite = inf
+        score_p, score_s = score_p + psnr[:, t].cpu(), score_s + ssim[:, t].cpu()
+    bp, bs = best_sample(score_p / (T - n_prime)), best_sample(score_s / (T - n_prime))
+    curves = torch.zeros(T, 8, dtype=torch.float64)
+    for t in range(n_prime, T):
+        row = curves[t]
+        p = float(psnr[bp, t])
+        if math.isfinite(p):
+            row[0], row[1] = p, 1.0
+        row[2] = float(ssim[bs, t])
+        for s in range(S):                                   # ascending s
+            p = float(psnr[s, t])
+            if math.isfinite(p):
+                row[3] += p
+                row[4] += 1.0
+            row[5] += float(ssim[s, t])
+        row[6], row[7] = 1.0, float(S)
+    return torch.tensor([bp, bs], dtype=torch.int64), curves
+
+
+def prediction_quality_reference(samples, target, n_prime, data_range, dtype=torch.float64):
+    """Best-of-N quality of S sampled videos against one target, the rule of `PredictionQualityEvaluator` (its CPU branch, and what
+    `lvt_amd.hip.ew.prediction_quality` is tested against).  samples (S, T, C, H, W), target (T, C, H, W): frames in
+    pixel space [0, data_range]; the first `n_prime` frames prime the sampler and are left out everywhere.
+    -> (psnr (S, T), ssim (S, T), best (2,) int64, curves (T, 8) float64).  psnr[s], ssim[s] are `frame_quality_reference(
+    samples[s], target)`.  The score of a sample under a metric is the mean of its values over t = n_prime .. T-1, added in
+    ascending t (a +inf psnr takes part); best = (the sample with the largest psnr score, the one with the largest ssim score),
+    chosen independently by `best_sample`.  curves is the clip's contribution to the per-step sums: rows below n_prime 0, row t
+      0: psnr[best[0], t] if finite, else 0    1: 1 if it is finite, else 0    2: ssim[best[1], t]
+      3: sum over s of the finite psnr[s, t]   4: their number                 5: sum over s of ssim[s, t]
+      6: 1 (clips)                             7: S (sampled videos)."""
+    if samples.dim() != 5 or samples.shape[0] < 1:
+        raise ValueError("prediction quality: samples are (S, T, C, H, W) with S >= 1, got %s" % (tuple(samples.shape),))
+    if target.dim() != 4:
+        raise ValueError("prediction quality: the target is (T, C, H, W), got %s" % (tuple(target.shape),))
+    n_prime = int(n_prime)
+    if not 0 <= n_prime < target.shape[0]:
+        raise ValueError("prediction quality: n_prime=%d outside [0, T=%d)" % (n_prime, target.shape[0]))
+    per_sample = [frame_quality_reference(samples[s], target, data_range, dtype) for s in range(samples.shape[0])]
+    psnr, ssim = torch.stack([p for p, _ in per_sample]), torch.stack([q for _, q in per_sample])
+    best, curves = prediction_select_reference(psnr, ssim, n_prime)
+    return psnr, ssim, best, curves
 
 
 def ssim_loss_reference(x, y, mean, std, data_range, lam):

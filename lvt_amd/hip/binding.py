@@ -245,6 +245,8 @@ def _declare(lib):
         "lvt_frame_quality_partials": (cll, [ci, ci, ci]),
         "lvt_frame_quality": (ci, [vp, vp, ci, ci, ci, ci, C.c_double, vp, cll, vp]),
         "lvt_frame_quality_finish": (ci, [vp, ci, ci, ci, ci, C.c_double, cll, vp, vp, vp]),
+        "lvt_frame_quality_vs": (ci, [vp, vp, ci, ci, ci, ci, ci, C.c_double, vp, cll, vp]),
+        "lvt_prediction_select": (ci, [vp, ci, ci, ci, vp, vp, vp]),
         "lvt_ssim_loss_partials": (cll, [ci, ci, ci, ci]),
         "lvt_ssim_loss_fwd": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, vp, C.c_double, C.c_double, vp, cll, vp, vp]),
         "lvt_ssim_loss_finish": (ci, [vp, cll, ci, ci, ci, ci, C.c_double, vp, vp]),

@@ -80,6 +80,59 @@ def frame_quality(a, b, data_range, acc=None, frames=None):
     return frames, acc
 
 
+def prediction_quality(samples, target, n_prime, data_range, curves=None, chunk_frames=512):
+    """Best-of-N quality of S sampled videos against one target (csrc/quality.hip; the rule:
+    lvt_amd.evaluation.quality.prediction_quality_reference).  samples (S, T, C, H, W), target (T, C, H, W): fp32 device frames in
+    [0, data_range]; the first `n_prime` frames are left out of the scores and the curves.  -> (frames, best, curves): frames
+    (S * T, 2) float64 = [psnr, ssim] of frame t of sample s against frame t of the target, sample-major; best (2,) int32 = the
+    sample with the largest mean psnr / ssim over the predicted steps; curves (T, 8) float64 += this clip's row per step (columns:
+    include/lvt_hip.h lvt_prediction_select; a fresh zeroed one when none is passed).  The compare runs over whole samples, at most
+    `chunk_frames` frames (and at least one sample) per lvt_frame_quality_vs / lvt_frame_quality_finish pair, each pair writing
+    its slice of the one table; the target is never copied.  One lvt_prediction_select follows.  Nothing is read on the host, and
+    a refused call launches nothing."""
+    if not torch.is_tensor(samples) or not torch.is_tensor(target):
+        raise L.LvtError("prediction_quality: tensors expected")
+    L.require(samples, target, curves)
+    if samples.dim() != 5 or target.dim() != 4 or samples.numel() == 0 or tuple(samples.shape[1:]) != tuple(target.shape):
+        raise L.LvtError("prediction_quality: shapes differ or are empty, samples (S, T, C, H, W) %s against target (T, C, H, W) %s"
+                         % (tuple(samples.shape), tuple(target.shape)))
+    if samples.dtype != torch.float32 or target.dtype != torch.float32:
+        raise L.LvtError("prediction_quality: float32 frames only, got %s and %s" % (samples.dtype, target.dtype))
+    if samples.device != target.device:
+        raise L.LvtError("prediction_quality: samples on %s, target on %s" % (samples.device, target.device))
+    S, T, Cc, H, W = samples.shape
+    if H < 11 or W < 11:
+        raise L.LvtError("prediction_quality: H=%d W=%d, the 11x11 window needs H and W >= 11" % (H, W))
+    data_range, n_prime, chunk_frames = float(data_range), int(n_prime), int(chunk_frames)
+    if not 0.0 < data_range < float("inf"):
+        raise L.LvtError("prediction_quality: data_range must be positive and finite, got %r" % (data_range,))
+    if not 0 <= n_prime < T:
+        raise L.LvtError("prediction_quality: n_prime=%d outside [0, T=%d)" % (n_prime, T))
+    if chunk_frames < 1:
+        raise L.LvtError("prediction_quality: chunk_frames=%d, at least 1" % chunk_frames)
+    if curves is None:
+        curves = torch.zeros(T, 8, dtype=torch.float64, device=samples.device)
+    elif curves.dtype != torch.float64 or tuple(curves.shape) != (T, 8) or curves.device != samples.device:
+        raise L.LvtError("prediction_quality: curves is (%d, 8) float64 on the frames' device" % T)
+    per = max(1, chunk_frames // T)                          # whole samples per launch pair
+    n = L.lib().lvt_frame_quality_partials(Cc, H, W)
+    if min(per, S) * T * n >= 1 << 31:
+        raise L.LvtError("prediction_quality: %d frames of %d tiles in one launch, lower chunk_frames" % (min(per, S) * T, n))
+    ws = L.workspace(min(per, S) * T * n * 16, samples.device, "frame_quality")
+    frames = torch.empty(S * T, 2, dtype=torch.float64, device=samples.device)
+    acc = torch.zeros(4, dtype=torch.float64, device=samples.device)          # scratch: `finish` needs one, nobody reads it
+    best = torch.empty(2, dtype=torch.int32, device=samples.device)
+    for s0 in range(0, S, per):
+        F = (min(s0 + per, S) - s0) * T
+        L.check(L.lib().lvt_frame_quality_vs(L.ptr(samples[s0]), L.ptr(target), F, T, Cc, H, W, data_range, L.ptr(ws), n,
+                                             L.stream_ptr()), "lvt_frame_quality_vs")
+        L.check(L.lib().lvt_frame_quality_finish(L.ptr(ws), F, Cc, H, W, data_range, n, L.ptr(frames[s0 * T]), L.ptr(acc),
+                                                 L.stream_ptr()), "lvt_frame_quality_finish")
+    L.check(L.lib().lvt_prediction_select(L.ptr(frames), S, T, n_prime, L.ptr(curves), L.ptr(best), L.stream_ptr()),
+            "lvt_prediction_select")
+    return frames, best, curves
+
+
 def ssim_loss_fwd(xt, x, mean, std, data_range, lam, want_grad=False):
     """The SSIM term of the reconstruction loss on channels-last activations (csrc/ssim_loss.hip; the rule:
     lvt_amd.evaluation.quality.ssim_loss_reference).  xt (the reconstruction), x (the target): (N, 1, H, W, Cp) fp32 device

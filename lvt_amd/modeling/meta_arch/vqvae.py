@@ -6,6 +6,7 @@ losses: lambda * mse(x_tilde, x)  and  beta * mse(z_e, sg(z_q_bar)).
 """
 import os
 
+from ...hip import ew
 from ...solver import build_lr_scheduler, build_optimizer
 from ...utils.checkpoint import Checkpointer
 from ..loss import ReconstructionLoss
@@ -117,6 +118,16 @@ class VQVAEModel(AutoEncoderModel):
         self._require_gpu()
         y = self._decode_cl(latents.to(self.device))
         return convstack.cl_to_nchw(y, self.generator.out_channels)
+
+    def decode_pixels(self, latents):
+        """(N,num,h,w) int64 codes -> (N,C,H,W) fp32 pixels in [0, hi], hi = 1 with INPUT.SCALE_TO_ZEROONE and 255 without: the
+        decoder's output de-normalised and clamped by the one kernel the `inference` mode ends with."""
+        self._require_gpu()
+        y = self._decode_cl(latents.to(self.device))
+        n, _, h, w, cp = y.shape
+        hi = 1.0 if self.cfg.INPUT.SCALE_TO_ZEROONE else 255.0
+        return ew.to_channels_first(y.view(n, h * w, cp), self.generator.out_channels, 2, self._pixel_mean, self._pixel_std,
+                                    0.0, hi).view(n, -1, h, w)
 
     def configure_optimizers_and_checkpointers(self):
         o, c = super().configure_optimizers_and_checkpointers()

@@ -188,7 +188,8 @@ class VideoTransformerModel(nn.Module):
             output = [{} for _ in range(len(data))]
             if "BitsEvaluator" in self.cfg.TEST.EVALUATORS:
                 output = self.calculate_logits_for_entire_video(data, output)
-            if "VTSampler" in self.cfg.TEST.EVALUATORS:
+            # one sampling pass feeds both evaluators that read `samples`
+            if "VTSampler" in self.cfg.TEST.EVALUATORS or "PredictionQualityEvaluator" in self.cfg.TEST.EVALUATORS:
                 output = self.sample_videos(data, output, n_prime=self.cfg.TEST.VT_SAMPLER.N_PRIME,
                                             num_samples=self.cfg.TEST.VT_SAMPLER.NUM_SAMPLES)
             assert len(output[0]) > 0
