@@ -563,6 +563,17 @@ int lvt_decode_commit(const long long *drawn, int rows, int S1, long long *codes
 int lvt_sample_categorical(const float *logits, long long rows, int V, float temp, const float *u,
                            long long *out, long long out_stride, float *probs, const int *pos, long long u_pos,
                            void *stream);
+/* the same draw from a truncated distribution, for the same limits (V <= 2048, temp > 0, `pos` / `u_pos`, optional
+ * `probs`) plus top_k >= 0 and 0 < top_p <= 1.  Top-k first: with 0 < top_k < V only the logits >= the top_k-th largest
+ * stay (compared as fp32 values, ties at the boundary all stay; 0 or >= V keeps everything).  Then top-p on what is left:
+ * with top_p < 1 the most likely codes stay, whole tie classes at a time, until their mass reaches top_p of the kept
+ * mass (masses are fp32 sums in one fixed order; the arg-max always stays).  probs = w / sum of the kept w, exactly 0
+ * on a cut code; code = #{ j : cdf_j <= u * total } over the kept weights in memory order, moved to the first kept index
+ * at or after it and to the last kept index past the end: a cut code is never returned.  top_k = 0 with top_p = 1 gives
+ * the codes and probs bits of lvt_sample_categorical.  Fixed summation order, no atomics, no LDS.                     */
+int lvt_sample_truncated(const float *logits, long long rows, int V, float temp, int top_k, float top_p, const float *u,
+                         long long *out, long long out_stride, float *probs, const int *pos, long long u_pos,
+                         void *stream);
 
 /* ---- embedding bags: the one-hot Conv3d / Embedding sums / one-hot Linear inputs as gathers (K13,K15,K25)
  * out[b*P+pos][:] = bias + btable[bindex[b]] + sum_s table[tab_row[s] + idx[b*bstride + off[s] + pos]][:]

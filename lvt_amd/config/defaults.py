@@ -126,6 +126,10 @@ _TABLE = [
     ('TEST.VT_SAMPLER.VQ_VAE.CODEBOOK_WEIGHTS', ''),
     ('TEST.VT_SAMPLER.N_PRIME', 5),
     ('TEST.VT_SAMPLER.NUM_SAMPLES', 10),
+    # truncated sampling (modeling/autoregressive/sampling.py): temperature of every draw, top-k (0: off), top-p (1.0: off)
+    ('TEST.VT_SAMPLER.TEMPERATURE', 1.0),
+    ('TEST.VT_SAMPLER.TOP_K', 0),
+    ('TEST.VT_SAMPLER.TOP_P', 1.0),
     ('OUTPUT_DIR', './output'),
     ('SEED', -1),
     ('CUDNN_BENCHMARK', True),

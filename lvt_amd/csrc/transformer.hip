@@ -815,6 +815,137 @@ extern "C" int lvt_sample_categorical(const float *logits, long long rows, int V
     return LVT_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// the same draw from a truncated distribution: top-k first (every logit >= the k-th largest, ties kept), then top-p on
+// what is left (the most likely codes, whole tie classes, until their mass reaches top_p of the kept mass).  Same
+// layout and arithmetic as smp_row: with top_k off (0 or >= V) and top_p == 1 no search runs and the codes and probs
+// bits are smp_row's.  No sort and no LDS: a logit becomes an order-preserving unsigned key (0 marks "not in the
+// row" and, after a cut, "cut"; -0.0 is read as +0.0 so that keys tie exactly where the floats compare equal), and
+// each threshold is the largest 32-bit value T whose wave-wide tally over { key >= T } still reaches the target, built
+// bit by bit from the top: the tally is a count (ballots) for top-k and a sum of weights (lane sums in element order,
+// then the xor butterfly: one fixed order, so monotone in T and the same bits for the same inputs) for top-p.
+// The count past the threshold is clamped to the last kept index, never to a cut code.
+// ------------------------------------------------------------------------------------------------
+template <int MAXPER>
+__device__ __forceinline__ float smpt_mass(const unsigned (&key)[MAXPER], const float (&e)[MAXPER], unsigned cand) {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXPER; ++i) s += key[i] >= cand ? e[i] : 0.f;
+    return wsum(s);
+}
+template <int MAXPER>
+__device__ __forceinline__ void smpt_row(const float *__restrict__ logits, int V, float inv_temp, int top_k, float top_p,
+                                         const float *__restrict__ u, long long *__restrict__ out, long long out_stride,
+                                         float *__restrict__ probs, const int *__restrict__ pos, long long u_pos) {
+    // smp_row rounds x * inv_temp before it subtracts the maximum (the product feeds the maximum too).  Here x stays live
+    // for the keys, which invites a fused x * inv_temp - m with other bits: no contraction in this function.
+#pragma clang fp contract(off)
+    const int row = blockIdx.x, lane = threadIdx.x;
+    if (pos) u += (long long)pos[0] * u_pos;
+    const float *x = logits + (long long)row * V;
+    const int per = (V + 63) / 64;                      // consecutive elements per lane: cdf order == memory order
+    const int j0 = lane * per;
+    float e[MAXPER];
+    unsigned key[MAXPER];
+    float m = -3.4e38f;
+#pragma unroll
+    for (int i = 0; i < MAXPER; ++i) {
+        const bool in = i < per && j0 + i < V;
+        const float xv = in ? x[j0 + i] : 0.f;
+        unsigned b = __float_as_uint(xv);
+        if (b == 0x80000000u) b = 0u;
+        b ^= (b & 0x80000000u) ? 0xffffffffu : 0x80000000u;
+        key[i] = in ? (b ? b : 1u) : 0u;
+        e[i] = in ? xv * inv_temp : -3.4e38f;
+        m = fmaxf(m, e[i]);
+    }
+    m = wmax(m);
+#pragma unroll
+    for (int i = 0; i < MAXPER; ++i) e[i] = (i < per && j0 + i < V) ? expf(e[i] - m) : 0.f;
+    if (top_k > 0 && top_k < V) {
+        unsigned T = 0u;
+        for (int bit = 31; bit >= 0; --bit) {
+            const unsigned cand = T | (1u << bit);
+            int c = 0;
+#pragma unroll
+            for (int i = 0; i < MAXPER; ++i) c += __popcll(__ballot(key[i] >= cand));
+            if (c >= top_k) T = cand;
+        }
+#pragma unroll
+        for (int i = 0; i < MAXPER; ++i) if (key[i] < T) { key[i] = 0u; e[i] = 0.f; }
+    }
+    if (top_p < 1.f) {
+        const float target = top_p * smpt_mass<MAXPER>(key, e, 1u);
+        unsigned T = 0u;
+        for (int bit = 31; bit >= 0; --bit) {
+            const unsigned cand = T | (1u << bit);
+            if (smpt_mass<MAXPER>(key, e, cand) >= target) T = cand;
+        }
+#pragma unroll
+        for (int i = 0; i < MAXPER; ++i) if (key[i] < T) { key[i] = 0u; e[i] = 0.f; }
+    }
+    float loc = 0.f;
+    int last = 0;
+#pragma unroll
+    for (int i = 0; i < MAXPER; ++i) { loc += e[i]; if (key[i]) last = j0 + i; }
+    // exclusive scan of the lane sums
+    float incl = loc;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const float t = __shfl_up(incl, d, 64); if (lane >= d) incl += t; }
+    const float total = __shfl(incl, 63, 64);
+    const float thr = u[row] * total;
+    float c = incl - loc;
+    int cnt = 0;
+#pragma unroll
+    for (int i = 0; i < MAXPER; ++i) { c += e[i]; if (i < per && j0 + i < V && c <= thr) ++cnt; }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
+    // In exact arithmetic index cnt is a kept one (its weight is what lifted the cdf over the threshold).  The cdf of a lane's
+    // first element comes from the scan and that of the lane before from its running sum, so in fp32 the count may stop on a
+    // cut index next to a lane boundary: take the first kept index at or after it, and the last kept one when there is none.
+    int nxt = 0x7fffffff;
+#pragma unroll
+    for (int i = MAXPER - 1; i >= 0; --i) if (key[i] && j0 + i >= cnt) nxt = j0 + i;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) { nxt = min(nxt, __shfl_xor(nxt, d, 64)); last = max(last, __shfl_xor(last, d, 64)); }
+    if (lane == 0) out[row * out_stride] = nxt < last ? nxt : last;
+    if (probs)
+#pragma unroll
+        for (int i = 0; i < MAXPER; ++i) if (i < per && j0 + i < V) probs[(long long)row * V + j0 + i] = e[i] / total;
+}
+__global__ __launch_bounds__(64) void lvt_sample_truncated_kernel(const float *__restrict__ logits, int V, float inv_temp, int top_k,
+                                                                  float top_p, const float *__restrict__ u,
+                                                                  long long *__restrict__ out, long long out_stride,
+                                                                  float *__restrict__ probs, const int *__restrict__ pos,
+                                                                  long long u_pos) {
+    smpt_row<SMP_MAXPER>(logits, V, inv_temp, top_k, top_p, u, out, out_stride, probs, pos, u_pos);
+}
+__global__ __launch_bounds__(64) void lvt_sample_truncated_wide_kernel(const float *__restrict__ logits, int V, float inv_temp,
+                                                                       int top_k, float top_p, const float *__restrict__ u,
+                                                                       long long *__restrict__ out, long long out_stride,
+                                                                       float *__restrict__ probs, const int *__restrict__ pos,
+                                                                       long long u_pos) {
+    smpt_row<2 * SMP_MAXPER>(logits, V, inv_temp, top_k, top_p, u, out, out_stride, probs, pos, u_pos);
+}
+
+extern "C" int lvt_sample_truncated(const float *logits, long long rows, int V, float temp, int top_k, float top_p, const float *u,
+                                    long long *out, long long out_stride, float *probs, const int *pos, long long u_pos,
+                                    void *stream) {
+    LVT_REQUIRE(logits && u && out && rows > 0 && V > 0 && V <= 128 * SMP_MAXPER && temp > 0.f, "sample_truncated: bad args");
+    LVT_REQUIRE(top_k >= 0 && top_p > 0.f && top_p <= 1.f, "sample_truncated: top_k=%d (>= 0), top_p=%g (in (0, 1])", top_k,
+                (double)top_p);
+    if (V > 64 * SMP_MAXPER) {
+        hipLaunchKernelGGL(lvt_sample_truncated_wide_kernel, dim3((unsigned)rows), dim3(64), 0, (hipStream_t)stream, logits, V,
+                           1.f / temp, top_k, top_p, u, out, out_stride, probs, pos, u_pos);
+        LVT_CHECK_LAUNCH("lvt_sample_truncated_wide_kernel");
+        return LVT_OK;
+    }
+    hipLaunchKernelGGL(lvt_sample_truncated_kernel, dim3((unsigned)rows), dim3(64), 0, (hipStream_t)stream, logits, V,
+                       1.f / temp, top_k, top_p, u, out, out_stride, probs, pos, u_pos);
+    LVT_CHECK_LAUNCH("lvt_sample_truncated_kernel");
+    return LVT_OK;
+}
+
 extern "C" int lvt_attn_decode(const float *q, long long ldq, const float *Kc, const float *Vc, int B, int H, int S, int da, int qi,
                                float temper, const float *dt, const float *dh, const float *dw, int bt, int bh, int bw,
                                float *o, const int *pos, long long q_pos, void *stream) {

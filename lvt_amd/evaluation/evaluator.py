@@ -284,6 +284,8 @@ class PredictionQualityEvaluator(DatasetEvaluator):
         self.vqvae, scale_to_zeroone = build_sampler_vqvae(cfg, vqvae)
         self._data_range = 1.0 if scale_to_zeroone else 255.0
         self._n_prime = int(cfg.TEST.VT_SAMPLER.N_PRIME)
+        s = cfg.TEST.VT_SAMPLER             # how the samples were drawn: reported only when it is not the default
+        self._sampling = {"temperature": float(s.TEMPERATURE), "top_k": int(s.TOP_K), "top_p": float(s.TOP_P)}
         self.reset()
 
     def reset(self):
@@ -361,6 +363,8 @@ class PredictionQualityEvaluator(DatasetEvaluator):
                "PSNR_mean": ratio(tot[3], tot[4]), "SSIM_mean": ratio(tot[5], tot[7]), "per_frame": per_frame,
                "clips": clips, "samples": int(rows[0, 7]) if len(steps) else 0, "n_prime": self._n_prime,
                "identical_best_frames": int(tot[6] - tot[1]), "target": "decoded_codes"}
+        if self._sampling != {"temperature": 1.0, "top_k": 0, "top_p": 1.0}:
+            res["sampling"] = dict(self._sampling)
         results = OrderedDict({"prediction_quality": res})
         if self._output_dir:
             os.makedirs(self._output_dir, exist_ok=True)

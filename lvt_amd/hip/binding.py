@@ -211,6 +211,7 @@ def _declare(lib):
         "lvt_decode_gather_codes": (ci, [vp, vp, vp, ci, ci, ci, vp, vp]),
         "lvt_decode_commit": (ci, [vp, ci, ci, vp, vp, vp]),
         "lvt_sample_categorical": (ci, [vp, cll, ci, cf, vp, vp, cll, vp, vp, cll, vp]),
+        "lvt_sample_truncated": (ci, [vp, cll, ci, cf, ci, cf, vp, vp, cll, vp, vp, cll, vp]),
         "lvt_embbag_fwd": (ci, [vp, cll, ci, cll, ci, P(ci), P(ci), vp, ci, vp, vp, vp, vp, vp]),
         "lvt_onehot_tn_workspace_bytes": (sz, [ci, ci, ci, cll]),
         "lvt_onehot_tn_is_gather": (ci, [ci, ci, ci, cll, vp, ci]),

@@ -279,6 +279,20 @@ def sample_categorical(logits, temp, u, out, out_stride=1, want_probs=False, pos
     return probs
 
 
+def sample_truncated(logits, temp, top_k, top_p, u, out, out_stride=1, want_probs=False, pos=None, u_pos=0):
+    """sample_categorical from the distribution cut to the top_k largest logits (0: no cut; ties at the k-th all stay) and
+    then to the smallest set of most likely codes whose mass reaches top_p (1.0: no cut); the probabilities returned are
+    those of the kept set, exactly 0 elsewhere, and a cut code is never drawn
+    (modeling/autoregressive/sampling.py states the rule)."""
+    L.require(logits, pos)
+    rows, V = logits.shape
+    probs = torch.empty(rows, V, dtype=torch.float32, device=logits.device) if want_probs else None
+    L.check(L.lib().lvt_sample_truncated(L.ptr(logits), rows, V, float(temp), int(top_k), float(top_p), C.c_void_p(u.data_ptr()),
+                                         C.c_void_p(out.data_ptr()), out_stride, L.ptr(probs), L.ptr(pos), u_pos, L.stream_ptr()),
+            "lvt_sample_truncated")
+    return probs
+
+
 def decode_gather_codes(codes_ext, nb, pos):
     """codes_ext (rows, S+1) int64, nb (S, taps) int64, pos int32 device scalar -> (rows, taps) codes of the causal
     neighbours of the current position."""

@@ -223,10 +223,13 @@ class GraphedSliceSampler:
     A step is ~110 tiny launches (M = batch rows); eagerly it is bound by host launch overhead (~3.7 ms/step measured at
     16 videos).  Because the position is a device-side cursor the launch sequence AND its arguments are identical for
     every position: the first step of each flavour (drawing / cache-filling only) runs eagerly and is then captured once;
-    every later position of every slice replays that graph.  LVT_DECODE_GRAPHS=0 keeps every step eager."""
+    every later position of every slice replays that graph.  LVT_DECODE_GRAPHS=0 keeps every step eager.
+    `temp`, `top_k` and `top_p` (truncated sampling, sampling.py) are arguments of the captured launches: a sampler is built
+    for one setting of the three."""
 
-    def __init__(self, vt_module, b, thw, temp=1.0):
+    def __init__(self, vt_module, b, thw, temp=1.0, top_k=0, top_p=1.0):
         self.vt, self.b, self.thw, self.temp = vt_module, b, thw, temp
+        self.top_k, self.top_p = top_k, top_p
         self.dec = None
         self.sl = None
         self.graphs = {}
@@ -253,7 +256,8 @@ class GraphedSliceSampler:
         dec = self.dec
         y = dec.step_at_cursor()
         drawn = self.vt.ch_predictor.sample_from_rows(y, self.temp, uniforms=self.uniforms, pos=dec.pos,
-                                                      split_ws=dec._split_ws).reshape(-1) if sample else None     # (b*nc,)
+                                                      split_ws=dec._split_ws, top_k=self.top_k,
+                                                      top_p=self.top_p).reshape(-1) if sample else None     # (b*nc,)
         tx.decode_commit(dec.sl_ext.view(dec.b * dec.nc, dec.S + 1), dec.pos, drawn)
 
     def step(self, pos, sample):

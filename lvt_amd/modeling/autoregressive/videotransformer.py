@@ -21,6 +21,7 @@ from ...hip.dropout import DropoutState, check_rate
 from .. import convstack
 from .autoregressive import Autoregressive
 from .build import AUTOREGRESSIVE_REGISTRY
+from .sampling import truncation_off
 from .vt_attention import BlockLocalAttention, PositionalEncoding, linear_wgrad
 
 
@@ -406,14 +407,15 @@ class ChannelPredictor(nn.Module):
             outs = tuple(_TiedOutputFn.apply(o, tables[k]) for k, o in enumerate(outs))
         return outs
 
-    def sample_pixel_tokens(self, yl_tok, b, P, pos, temp=1.0, forced_codes=None, return_probs=False):
+    def sample_pixel_tokens(self, yl_tok, b, P, pos, temp=1.0, forced_codes=None, return_probs=False, top_k=0, top_p=1.0):
         """One pixel of every sample: sequentially draw the nc channels (videotransformer.py:161-185).
         yl_tok (b*P, d); pos = flat position inside the slice.  Returns codes (b, nc) int64.
         `forced_codes` (b, nc) replaces the draws (teacher forcing, used to check the per-channel
-        probabilities against the reference since torch.multinomial streams are device specific)."""
+        probabilities against the reference since torch.multinomial streams are device specific).
+        `top_k` / `top_p`: truncated sampling (sampling.py), off at 0 / 1.0."""
         d = yl_tok.shape[-1]
         rows = yl_tok.view(b, P, d)[:, pos].contiguous()                      # (b, d)
-        return self.sample_from_rows(rows, temp, forced_codes, return_probs)
+        return self.sample_from_rows(rows, temp, forced_codes, return_probs, top_k=top_k, top_p=top_p)
 
     def prepare_decode(self):
         """Transposed copies of the one-hot columns of U_k ((k*nv, d) gather tables), refreshed IN PLACE so that
@@ -425,11 +427,16 @@ class ChannelPredictor(nn.Module):
         for k in range(1, self.nc):
             self._ut[k].copy_(self.U[k].weight.detach()[:, d:d + k * self.nv].t())
 
-    def sample_from_rows(self, rows, temp=1.0, forced_codes=None, return_probs=False, uniforms=None, pos=None, split_ws=None):
+    def sample_from_rows(self, rows, temp=1.0, forced_codes=None, return_probs=False, uniforms=None, pos=None, split_ws=None,
+                         top_k=0, top_p=1.0):
         """rows (b, d): decoder hidden state of ONE position per sample -> codes (b, nc).
         `uniforms` (P, nc, b) with the int32 device cursor `pos`: the draws of position pos[0] come from uniforms[pos[0]]
-        (a table filled once per slice: the decode graphs contain no random-number generator)."""
+        (a table filled once per slice: the decode graphs contain no random-number generator).
+        `top_k` / `top_p`: every draw is from the distribution cut by lvt_sample_truncated (the rule: sampling.py); with both
+        off (0 / 1.0) the launches are those of untruncated sampling.  With `forced_codes` the probabilities returned are
+        the truncated ones, from the same kernel."""
         b, d = rows.shape
+        cut = not truncation_off(top_k, top_p)
         cached = getattr(self, "_ut", None)
         tables = self._tables()
         y, _, _ = ew.layernorm_fwd(rows, self.layer_norm.weight, self.layer_norm.bias, save_stats=False)
@@ -458,14 +465,24 @@ class ChannelPredictor(nn.Module):
             if forced_codes is None:
                 # writes codes[:, k, 0] (element stride nc between samples)
                 if uniforms is not None:
-                    pr = tx.sample_categorical(o, temp, uniforms.view(-1)[k * b:], codes.view(-1)[k:], self.nc,
-                                               want_probs=return_probs, pos=pos, u_pos=self.nc * b)
+                    if cut:
+                        pr = tx.sample_truncated(o, temp, top_k, top_p, uniforms.view(-1)[k * b:], codes.view(-1)[k:], self.nc,
+                                                 want_probs=return_probs, pos=pos, u_pos=self.nc * b)
+                    else:
+                        pr = tx.sample_categorical(o, temp, uniforms.view(-1)[k * b:], codes.view(-1)[k:], self.nc,
+                                                   want_probs=return_probs, pos=pos, u_pos=self.nc * b)
+                elif cut:
+                    pr = tx.sample_truncated(o, temp, top_k, top_p, u[k], codes.view(-1)[k:], self.nc, want_probs=return_probs)
                 else:
                     pr = tx.sample_categorical(o, temp, u[k], codes.view(-1)[k:], self.nc, want_probs=return_probs)
                 if return_probs:
                     probs.append(pr)
             else:
-                probs.append(torch.softmax(o / temp, 1))
+                if cut:      # the kept set and its probabilities come from the kernel; its draw is overwritten by the forced code
+                    probs.append(tx.sample_truncated(o, temp, top_k, top_p, torch.zeros(b, device=o.device), codes.view(-1)[k:],
+                                                     self.nc, want_probs=True))
+                else:
+                    probs.append(torch.softmax(o / temp, 1))
                 codes[:, k, 0] = forced_codes[:, k].to(codes.device)
         if return_probs:
             return codes[:, :, 0], torch.stack(probs, 1)

@@ -15,6 +15,7 @@ from ...solver import build_lr_scheduler, build_optimizer
 from ...utils.checkpoint import Checkpointer
 from ...utils.events import get_event_storage
 from ..autoregressive import build_autoregressive
+from ..autoregressive.sampling import check_sampling, truncation_off
 from ..autoregressive.vt_attention import prefetch_p2_images
 from ..autoregressive.vt_utils import slice_and_context, subscale_order
 from .build import META_ARCH_REGISTRY
@@ -109,6 +110,7 @@ class VideoTransformerModel(nn.Module):
         self.model = build_autoregressive(cfg)
         self.init_weights(self.model, cfg.MODEL.INIT_TYPE)
         self.vis_period = cfg.VIS_PERIOD
+        self._sampling_settings()                # (ValueError that names the config key, GPU or not)
         self._reducers = []
         self.to(self.device)
 
@@ -140,6 +142,11 @@ class VideoTransformerModel(nn.Module):
     @property
     def _vt(self):
         return self.cfg.MODEL.AUTOREGRESSIVE.VT
+
+    def _sampling_settings(self):
+        """(temp, top_k, top_p) of TEST.VT_SAMPLER.{TEMPERATURE, TOP_K, TOP_P}, checked."""
+        s = self.cfg.TEST.VT_SAMPLER
+        return check_sampling(s.TEMPERATURE, s.TOP_K, s.TOP_P)
 
     # ---- supervised ------------------------------------------------------------------------------------
     def preprocess_data(self, data):
@@ -224,8 +231,9 @@ class VideoTransformerModel(nn.Module):
 
     # ---- sampling (vt.py:82-136, 210-228) -----------------------------------------------------------------
     @torch.no_grad()
-    def sample_video(self, video, temp=1.0, n_prime=1, class_idx=None, incremental=True):
+    def sample_video(self, video, temp=1.0, n_prime=1, class_idx=None, incremental=True, top_k=0, top_p=1.0):
         """video (B, nc, T, H, W) int64 with the first n_prime frames given; returns the completed grid.
+        `top_k` / `top_p`: truncated sampling (autoregressive/sampling.py), off at 0 / 1.0; both schedules honour them.
 
         incremental=True (default): encoder once per slice, then ONE single-token decoder step per position
         against K/V caches (modeling/autoregressive/incremental.py), for every slice that is a multiple of each
@@ -233,6 +241,7 @@ class VideoTransformerModel(nn.Module):
         reproduces the reference's schedule (full decoder pass per generated pixel, vt.py:121-131); both draw from
         the same per-pixel distributions."""
         from ..autoregressive.incremental import GraphedSliceSampler, IncrementalDecoder
+        _, top_k, top_p = check_sampling(temp, top_k, top_p)
         self._require_gpu()
         v = self._vt
         video = video.to(self.device).clone()
@@ -257,6 +266,8 @@ class VideoTransformerModel(nn.Module):
             # streams (own K/V caches and graphs) whose steps interleave on the GPU.  Measured on 1 MI355X, frames/s:
             # 527 (64 videos), 932 (128), 1341 (256), 1696 (512) in one group; 1956 for 3 groups of 256.
             key = (B, t, h, w, float(temp))
+            if not truncation_off(top_k, top_p):
+                key += (top_k, top_p)
             groups = self._samplers.get(key) if hasattr(self, "_samplers") else None
             if groups is None:
                 rows = decode_group_rows(IncrementalDecoder.bytes_per_video(self.model.decoder, (t, h, w)),
@@ -264,11 +275,13 @@ class VideoTransformerModel(nn.Module):
                 if rows < DECODE_GROUP_ROWS and B > MAX_CONCURRENT_GROUPS * rows:   # memory-bound: one wave of groups per pass
                     n = MAX_CONCURRENT_GROUPS * rows
                     return torch.cat([self.sample_video(video[i:i + n], temp, n_prime,
-                                                        None if class_idx is None else class_idx[i:i + n])
+                                                        None if class_idx is None else class_idx[i:i + n], top_k=top_k,
+                                                        top_p=top_p)
                                       for i in range(0, B, n)])
                 ng = (B + rows - 1) // rows
                 bounds = [B * g // ng for g in range(ng + 1)]
-                groups = [(bounds[g], bounds[g + 1], GraphedSliceSampler(self.model, bounds[g + 1] - bounds[g], (t, h, w), temp),
+                groups = [(bounds[g], bounds[g + 1],
+                           GraphedSliceSampler(self.model, bounds[g + 1] - bounds[g], (t, h, w), temp, top_k, top_p),
                            (torch.cuda.Stream(device=video.device) if DECODE_GROUP_STREAMS else
                             torch.cuda.current_stream(video.device)) if ng > 1 else None) for g in range(ng)]
                 self._samplers = {key: groups}            # keep the most recent geometry's graphs
@@ -323,12 +336,14 @@ class VideoTransformerModel(nn.Module):
                             if prime_sl[ti, hi, wi]:
                                 continue
                             yl = self.model.decoder.forward_tokens(sl, zl)
-                            sl[:, :, ti, hi, wi] = pred.sample_pixel_tokens(yl, B, t * h * w, (ti * h + hi) * w + wi, temp)
+                            sl[:, :, ti, hi, wi] = pred.sample_pixel_tokens(yl, B, t * h * w, (ti * h + hi) * w + wi, temp,
+                                                                            top_k=top_k, top_p=top_p)
             video[:, :, a::st, b_::sh, c::sw] = sl
         return video
 
     @torch.no_grad()
-    def sample_slice(self, context, slice_idx, slice_size, temp=0.9, class_idx=None):
+    def sample_slice(self, context, slice_idx, slice_size, temp=0.9, class_idx=None, top_k=0, top_p=1.0):
+        _, top_k, top_p = check_sampling(temp, top_k, top_p)
         sl = torch.zeros(size=slice_size, device=context.device, dtype=torch.long)
         B, _, t, h, w = sl.shape
         zl = self.model.encoder.forward_tokens(context.contiguous(), slice_idx.contiguous(), class_idx)
@@ -337,7 +352,7 @@ class VideoTransformerModel(nn.Module):
                 for wi in range(w):
                     yl = self.model.decoder.forward_tokens(sl, zl)
                     sl[:, :, ti, hi, wi] = self.model.ch_predictor.sample_pixel_tokens(
-                        yl, B, t * h * w, (ti * h + hi) * w + wi, temp)
+                        yl, B, t * h * w, (ti * h + hi) * w + wi, temp, top_k=top_k, top_p=top_p)
         return sl
 
     def sample_videos(self, data, output, n_prime=5, num_samples=1):
@@ -345,7 +360,9 @@ class VideoTransformerModel(nn.Module):
         video = video.transpose(1, 2).contiguous()                   # B, nc, T, H, W
         video[:, :, n_prime:] = 0
         class_idx = self._class_idx(data)
-        samples = [self.sample_video(video.clone(), n_prime=n_prime, class_idx=class_idx) for _ in range(num_samples)]
+        temp, top_k, top_p = self._sampling_settings()
+        samples = [self.sample_video(video.clone(), temp, n_prime=n_prime, class_idx=class_idx, top_k=top_k, top_p=top_p)
+                   for _ in range(num_samples)]
         assert video.size(0) == len(output)
         for i in range(video.size(0)):
             output[i]["samples"] = [s[i] for s in samples]
