@@ -852,6 +852,24 @@ int lvt_dropout_add(const float *z, const float *res, long long n, unsigned long
 int lvt_dropout_bwd(const float *g, long long n, unsigned long long seed, unsigned site_rank, unsigned pass, unsigned T, float s,
                     float *out, unsigned *out_amax, void *stream);
 
+/* ---- cosine codebook lookup (MODEL.CODEBOOK.COSINE; additive under ABI 680; csrc/l2norm.hip; the rule in plain torch:
+ * lvt_amd/modeling/vq/cosine.py).  x, y, g, dx: [rows][G * d] fp32, contiguous -- rows * G groups of d floats; inv: [rows][G].
+ *   fwd: inv = 1 / max(sqrt(sum of squares of the group), eps), y = x * inv: F.normalize(x, dim=-1, eps) per group.  y may be x
+ *        itself (in place).  inv is nullable (the codebook pass does not keep it).
+ *   bwd: dx = inv * (g - y * (y . g)), and dx = inv * g for a group whose norm was clamped, which is recognised by
+ *        inv == 1 / eps (the same fp32 quotient the forward stored): the backward of torch autograd's F.normalize for a norm
+ *        above eps and for one below it.  A norm within rounding of eps itself counts as clamped.
+ * d: a multiple of 16 from 16 to 1024; G * d: at most 4096 floats per row; eps: positive and finite.  out_amax (nullable):
+ * integer atomic max of the bit pattern of max |y| (max |dx|) over its finite elements, as on the other helper kernels.  The
+ * reductions run in one fixed order without LDS or atomics: the same arguments give the same bits.  The contract covers groups
+ * whose sum of squares is finite in fp32 (elements up to about 1e19 / sqrt(d); encoder outputs are O(1)).  A bad geometry, a
+ * null x / y / g / inv (bwd) / dx, or a misaligned pointer (16 bytes; 4 for inv and out_amax): LVT_EINVAL before any device
+ * work. */
+int lvt_l2norm_groups_fwd(const float *x, long long rows, int G, int d, float eps, float *y, float *inv, unsigned *out_amax,
+                          void *stream);
+int lvt_l2norm_groups_bwd(const float *g, const float *y, const float *inv, long long rows, int G, int d, float eps, float *dx,
+                          unsigned *out_amax, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

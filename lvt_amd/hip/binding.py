@@ -253,6 +253,8 @@ def _declare(lib):
         "lvt_ssim_loss_finish": (ci, [vp, cll, ci, ci, ci, ci, C.c_double, vp, vp]),
         "lvt_dropout_add": (ci, [vp, vp, cll, C.c_ulonglong, C.c_uint, C.c_uint, C.c_uint, cf, vp, vp, vp]),
         "lvt_dropout_bwd": (ci, [vp, cll, C.c_ulonglong, C.c_uint, C.c_uint, C.c_uint, cf, vp, vp, vp]),
+        "lvt_l2norm_groups_fwd": (ci, [vp, cll, ci, ci, cf, vp, vp, vp, vp]),
+        "lvt_l2norm_groups_bwd": (ci, [vp, vp, vp, cll, ci, ci, cf, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)

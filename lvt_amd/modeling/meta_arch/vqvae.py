@@ -3,6 +3,8 @@
 supervised step:  x -> ResEncoder -> z_e -> DVQ "st" (indices, z_q_st from the pre-update codebook,
 EMA update, z_q_bar from the post-update codebook) -> ResDecoder -> x_tilde;
 losses: lambda * mse(x_tilde, x)  and  beta * mse(z_e, sg(z_q_bar)).
+With MODEL.CODEBOOK.COSINE the quantiser and the commitment loss see u = z_e with every sub-vector l2-normalised instead of z_e
+(lvt_amd/modeling/vq/cosine.py).
 """
 import os
 
@@ -22,10 +24,11 @@ class VQVAEModel(AutoEncoderModel):
         super().__init__(cfg)
         cb = cfg.MODEL.CODEBOOK
         self.use_codebook_ema = cb.EMA
+        # (COSINE with EMA False is the quantisers' ValueError: a trained cosine codebook is not built)
         if cb.NUM == 1:          # the default of the config tree: `VQEmbedding` used directly (vqvae.py:25-27)
-            self.codebook = SingleVQEmbedding(cb.SIZE, cb.DIM, self.use_codebook_ema)
+            self.codebook = SingleVQEmbedding(cb.SIZE, cb.DIM, self.use_codebook_ema, cosine=cb.COSINE)
         else:
-            self.codebook = DVQEmbedding(cb.NUM, cb.SIZE, cb.DIM, self.use_codebook_ema)
+            self.codebook = DVQEmbedding(cb.NUM, cb.SIZE, cb.DIM, self.use_codebook_ema, cosine=cb.COSINE)
         if self.use_codebook_ema:
             self._set_requires_grad(self.codebook.parameters(), False)
         if cb.RESTART.ENABLED:
@@ -78,7 +81,8 @@ class VQVAEModel(AutoEncoderModel):
 
     # ---- channels-last internals --------------------------------------------------------------------
     def _latent_cl(self, x):
-        return self.codebook.indices_cl(self.encoder.forward_cl(x))          # (N,num,h,w) int64
+        z_e = self.encoder.forward_cl(x)
+        return self.codebook.indices_cl(self.codebook.normalise_cl(z_e))     # (N,num,h,w) int64
 
     def _latent_public(self, latent):
         return latent
@@ -87,7 +91,8 @@ class VQVAEModel(AutoEncoderModel):
         return self.generator.forward_cl(self.codebook.embed_cl(latent))
 
     def _supervised_loss_cl(self, x, return_x=False):
-        z_e = self.encoder.forward_cl(x)
+        # (COSINE: u, the l2-normalised sub-vectors, takes the place of z_e from here on; the identity when the key is off)
+        z_e = self.codebook.normalise_cl(self.encoder.forward_cl(x))
         # the decoder needs z_q_st only (pre-update codebook): the all-reduce of the EMA statistics that the quantiser
         # started runs beside the decoder forward and is joined afterwards (reference order of updates: vq_embedding.py:46-59)
         z_q_st = self.codebook.straight_through_cl(z_e, defer=True)

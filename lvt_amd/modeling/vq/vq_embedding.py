@@ -16,15 +16,19 @@ Deliberate, documented deviations:
     has been enqueued (meta_arch/vqvae.py).  Same arithmetic, same order of updates as the reference (vq_embedding.py:46-59).
   * `enable_restart` (MODEL.CODEBOOK.RESTART; the reference has nothing like it, off by default): dead codes are re-seeded from
     encoder rows of the pass inside the finalize launch, and a health record is kept (_RestartMixin).
+  * `cosine` (MODEL.CODEBOOK.COSINE; the reference has nothing like it, off by default): the lookup runs on the unit sphere.  The
+    caller hands the quantiser u = normalise_cl(z_e) instead of z_e, and the finalize step leaves unit rows in the codebook
+    (_CosineMixin; the rule in plain torch: cosine.py).
 """
 import torch
 from torch import nn
 
 from ...hip import binding as L
-from ...hip import ew, vq
+from ...hip import ew, l2norm, vq
 from ...layers.all_reduce import all_reduce_sum_async_
 from ...utils import comm
 from .. import convstack
+from . import cosine as cosine_rule
 
 SUPPORTED_GEOMETRY = ("sub-vector width DIM / NUM: a multiple of 16 from 16 to 256 (product quantiser, DVQEmbedding) or "
                       "DIM a multiple of 64 (one wide codebook, SingleVQEmbedding); codebook size SIZE: a multiple of 64 "
@@ -101,6 +105,8 @@ class _RestartMixin:
         else:
             vq.ema_finalize_restart(stats, cand, rsize, rsum, w, self._restart[0], self.restart_health, self.restart_total,
                                     self.restart_pass, self.decay, self.eps)
+        if self.cosine:
+            self._unit_codes(w)                           # (running_sum and running_size stay as the launch left them)
 
     def health_scalars(self):
         """(perplexity: mean over codebooks, dead: sum, restarts: cumulative sum) of the last finalized train pass as device
@@ -112,13 +118,58 @@ class _RestartMixin:
         return h[:, 0].mean(), h[:, 1].sum(), self.restart_total[:n].sum().double()
 
 
-class VQEmbedding(nn.Module):
-    """One codebook: parameter / buffer container (vq_embedding.py:9-21)."""
+class _NormaliseFn(torch.autograd.Function):
+    """u = F.normalize of every `d`-wide group of channels-last rows (rows, G d), with the backward of torch autograd's
+    F.normalize (cosine.py step 6): lvt_l2norm_groups_fwd / _bwd."""
 
-    def __init__(self, K, D, ema):
+    @staticmethod
+    def forward(ctx, z2d, d):
+        u, inv = l2norm.l2norm_groups_fwd(z2d, d)
+        ctx.save_for_backward(u, inv)
+        ctx.d = d
+        return u
+
+    @staticmethod
+    def backward(ctx, g):
+        u, inv = ctx.saved_tensors
+        return l2norm.l2norm_groups_bwd(g.contiguous(), u, inv, ctx.d), None
+
+
+class _CosineMixin:
+    """Cosine lookup (MODEL.CODEBOOK.COSINE) for the two quantisers: `normalise_cl` is the node z_e -> u that the
+    caller applies before `indices_cl` / `straight_through_cl`, and `_unit_codes` what the finalize step ends with.  The
+    parameters, buffers and state-dict keys are those of a quantiser without it."""
+
+    cosine = False
+    COSINE_MAX_WIDTH = 1024        # the widest group of lvt_l2norm_groups_fwd
+
+    def _check_cosine(self, ema, width):
+        if not ema:
+            raise ValueError("MODEL.CODEBOOK.COSINE needs MODEL.CODEBOOK.EMA: a trained cosine codebook would need a "
+                             "differentiable normalisation of its weights")
+        if width > self.COSINE_MAX_WIDTH:
+            raise NotImplementedError("MODEL.CODEBOOK.COSINE: one codebook of DIM %d; the normalisation kernels take groups of "
+                                      "at most %d" % (width, self.COSINE_MAX_WIDTH))
+
+    def normalise_cl(self, z_cl):
+        """(N,1,H,W,D) channels-last -> u of the same shape: every sub-vector (the whole row for the single codebook) divided
+        by its l2 norm.  The identity, and no launch, when the lookup is off."""
+        if not self.cosine:
+            return z_cl
+        L.require(z_cl)
+        return _NormaliseFn.apply(z_cl.view(-1, z_cl.shape[-1]), self.D // self.num).view(z_cl.shape)
+
+
+class VQEmbedding(nn.Module):
+    """One codebook: parameter / buffer container (vq_embedding.py:9-21).  unit: the rows are l2-normalised once after the
+    reference's init (MODEL.CODEBOOK.COSINE, cosine.py step 8)."""
+
+    def __init__(self, K, D, ema, unit=False):
         super().__init__()
         self.embedding = nn.Embedding(K, D)
         self.embedding.weight.data.uniform_(-1.0 / K, 1.0 / K)
+        if unit:
+            cosine_rule.init_(self.embedding.weight.data)
         self.K, self.D, self.ema = K, D, ema
         if ema:
             self.eps, self.decay = 1e-5, 0.99
@@ -206,7 +257,7 @@ class _SingleGatherWithGradFn(torch.autograd.Function):
         return None, None, stats[:, :, :64].permute(1, 0, 2).reshape(o.K, o.D).contiguous()
 
 
-class SingleVQEmbedding(_RestartMixin, VQEmbedding):
+class SingleVQEmbedding(_RestartMixin, _CosineMixin, VQEmbedding):
     """`VQEmbedding` used directly as the quantiser: CODEBOOK.NUM == 1, the default of the config tree (config/defaults.py:79,
     meta_arch/vqvae.py:25-27).  Same parameters, buffers and state_dict keys as the reference's class (`embedding.weight`,
     `running_size`, `running_sum`); latents carry no codebook axis: (N, H, W).
@@ -217,10 +268,12 @@ class SingleVQEmbedding(_RestartMixin, VQEmbedding):
     in every group) are exactly those of the wide codebook, and lvt_vq_ema_finalize applies the reference's update
     (vq_embedding.py:48-59) to every group with the same counts."""
 
-    def __init__(self, K, D, ema):
+    def __init__(self, K, D, ema, cosine=False):
         check_geometry(1, K, D, single=True)
-        super().__init__(K, D, ema)
-        self.num, self.groups = 1, D // 64
+        if cosine:
+            self._check_cosine(ema, D)
+        super().__init__(K, D, ema, unit=cosine)
+        self.num, self.groups, self.cosine = 1, D // 64, bool(cosine)
         self._pending = None
 
     # ---- 64-d group views ------------------------------------------------------------------------------------------------
@@ -239,6 +292,13 @@ class SingleVQEmbedding(_RestartMixin, VQEmbedding):
     def _group_idx(self, idx, P):
         """(rows,) -> (rows / P, g, P): every group selects with the same index."""
         return idx.view(-1, 1, P).expand(-1, self.groups, P).contiguous()
+
+    def _unit_codes(self, wg):
+        """The grouped codebook (g, K, 64) the finalize launch wrote -> unit rows, normalised as the (K, D) rows they are."""
+        rows = self._ungrouped(wg).contiguous()
+        l2norm.l2norm_groups_fwd(rows, self.D, inplace=True, want_inv=False)
+        with torch.no_grad():
+            wg.copy_(self._grouped(rows))
 
     def _flat(self):
         """The tensors a data-parallel run broadcasts from rank 0 (meta_arch/vqvae.py wrap_parallel)."""
@@ -295,23 +355,30 @@ class SingleVQEmbedding(_RestartMixin, VQEmbedding):
     # ---- the reference's call contract (vq_embedding.py:23-33) -------------------------------------------------------------
     def forward(self, z_e_x, mode=""):
         if mode == "":
-            return self.indices_cl(convstack._LayoutIn.apply(z_e_x))
+            return self.indices_cl(self.normalise_cl(convstack._LayoutIn.apply(z_e_x)))
         if mode == "st":
-            st, bar = self.straight_through_cl(convstack._LayoutIn.apply(z_e_x))
+            st, bar = self.straight_through_cl(self.normalise_cl(convstack._LayoutIn.apply(z_e_x)))
             return convstack._LayoutOut.apply(st, self.D), convstack._LayoutOut.apply(bar, self.D)
         if mode == "emb":
             return self.embed_cl(z_e_x).squeeze(1)           # (N, H, W, D), as nn.Embedding yields
         raise ValueError
 
 
-class DVQEmbedding(_RestartMixin, nn.Module):
-    def __init__(self, num, K, D, ema):
+class DVQEmbedding(_RestartMixin, _CosineMixin, nn.Module):
+    def __init__(self, num, K, D, ema, cosine=False):
         super().__init__()
         check_geometry(num, K, D)
-        self.num, self.D, self.K, self.ema = num, D, K, ema
+        if cosine:
+            self._check_cosine(ema, D // num)
+        self.num, self.D, self.K, self.ema, self.cosine = num, D, K, ema, bool(cosine)
         self.decay, self.eps = 0.99, 1e-5
-        self.ve = nn.ModuleList([VQEmbedding(K, D // num, ema) for _ in range(num)])
+        self.ve = nn.ModuleList([VQEmbedding(K, D // num, ema, unit=cosine) for _ in range(num)])
         self._flat_w = self._flat_rs = self._flat_rsum = None
+
+    def _unit_codes(self, w):
+        """The flat codebook buffer (num, K, d) the finalize launch wrote -> unit rows, in place, one launch (which records
+        max |w| in f16x2 mode and, as every raw-pointer write, retires the records of the other views of the buffer)."""
+        l2norm.l2norm_groups_fwd(w, self.D // self.num, inplace=True, want_inv=False)
 
     # ---- flat storage ----------------------------------------------------------------------------
     def _flat(self):
@@ -400,10 +467,10 @@ class DVQEmbedding(_RestartMixin, nn.Module):
     def forward(self, z_e_x, mode=""):
         if mode == "":
             assert z_e_x.dim() == 4
-            return self.indices_cl(convstack._LayoutIn.apply(z_e_x))
+            return self.indices_cl(self.normalise_cl(convstack._LayoutIn.apply(z_e_x)))
         if mode == "st":
             assert z_e_x.dim() == 4
-            st, bar = self.straight_through_cl(convstack._LayoutIn.apply(z_e_x))
+            st, bar = self.straight_through_cl(self.normalise_cl(convstack._LayoutIn.apply(z_e_x)))
             return convstack._LayoutOut.apply(st, self.D), convstack._LayoutOut.apply(bar, self.D)
         if mode == "emb":
             return self.embed_cl(z_e_x).squeeze(1)       # (N,H,W,D), as torch.cat(..., dim=-1) yields
