@@ -870,6 +870,34 @@ int lvt_l2norm_groups_fwd(const float *x, long long rows, int G, int d, float ep
 int lvt_l2norm_groups_bwd(const float *g, const float *y, const float *inv, long long rows, int G, int d, float eps, float *dx,
                           unsigned *out_amax, void *stream);
 
+/* ---- finite scalar quantisation (MODEL.CODEBOOK.FSQ.LEVELS; additive under 680) ------------------------------------
+ * The bound-and-round of projected rows, its straight-through backward and the decode from code indices; the rule is stated in
+ * plain torch in lvt_amd/modeling/vq/fsq.py.  Rows of num groups of d = levels.d floats with a row stride ld >= num * d floats,
+ * ld a multiple of 4 up to 4096; the pad columns [num * d, ld) of every float output are written as 0.  Per entry i of a group,
+ * with half_l = (L_i - 1)(1 + 1e-3) / 2, offset = 0.5 for an even L_i else 0, shift = atanh(offset / half_l), w = L_i / 2 (the
+ * constants are formed on the host in float64 and reach the kernel as floats, with the level table, in the launch arguments):
+ *   fwd:    b = tanh(z_p + shift) * half_l - offset, q = rint(b) (half to even), digit = q + w in [0, L_i - 1], z_q = q / w;
+ *           idx[(r / P) * num * P + g * P + r % P] = sum_i digit_i * prod_{j<i} L_j for row r and group g -- the (rows / P, num,
+ *           P) int64 layout of lvt_vq_nearest.  z_q or idx may be NULL (not both); P is read only with idx and must divide rows.
+ *   bwd:    dz_p = g * (half_l / w) * (1 - tanh^2(z_p + shift)).
+ *   decode: the digits of idx by successive division, z_q = (digit - w) / w: the bits lvt_fsq_fwd writes for the same code.
+ * Levels from 2 to 64, 1 to LVT_FSQ_MAX_LEVELS of them, prod(levels) at most 2^30.  out_amax (nullable): integer atomic max of the
+ * bit pattern of max |z_q| (max |dz_p|) over its finite elements, as on the other helper kernels.  Every element is a function
+ * of its own inputs: no reductions, no float atomics, the same arguments give the same bits; the grid is a function of `rows`.
+ * A bad geometry or level table, a null z_p / g / dz_p / idx (decode) / z_q (decode), or a misaligned pointer (16 bytes; 8 for
+ * idx, 4 for out_amax): LVT_EINVAL before any device work. */
+#define LVT_FSQ_MAX_LEVELS 11
+typedef struct lvt_fsq_levels {
+    int d;                               /* number of levels in use */
+    int levels[LVT_FSQ_MAX_LEVELS];      /* L_1 .. L_d; the rest is ignored */
+} lvt_fsq_levels;
+int lvt_fsq_fwd(const float *z_p, long long rows, int num, int ld, lvt_fsq_levels levels, int P, float *z_q, long long *idx,
+                unsigned *out_amax, void *stream);
+int lvt_fsq_bwd(const float *g, const float *z_p, long long rows, int num, int ld, lvt_fsq_levels levels, float *dz_p,
+                unsigned *out_amax, void *stream);
+int lvt_fsq_decode(const long long *idx, long long rows, int num, int ld, lvt_fsq_levels levels, int P, float *z_q,
+                   unsigned *out_amax, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

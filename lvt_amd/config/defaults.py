@@ -59,6 +59,7 @@ _TABLE = [
     ('MODEL.CODEBOOK.RESTART.ENABLED', False),       # re-seed dead EMA codes from encoder rows + codebook health
     ('MODEL.CODEBOOK.RESTART.THRESHOLD', 1.0),       # dead: running_size below it and no row won in the pass; 0.0: monitoring only
     ('MODEL.CODEBOOK.COSINE', False),                # l2-normalised (cosine) lookup on unit-row EMA codebooks
+    ('MODEL.CODEBOOK.FSQ.LEVELS', []),               # finite scalar quantisation, e.g. [8, 8, 8]: SIZE = prod(LEVELS)
     ('INPUT.FORMAT', 'L'),
     ('INPUT.N_FRAMES_PER_VIDEO_TRAIN', -1),
     ('INPUT.N_FRAMES_PER_VIDEO_TEST', -1),

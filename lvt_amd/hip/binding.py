@@ -112,6 +112,14 @@ class GradEntry(C.Structure):
     _fields_ = [("g", C.c_void_p), ("n", C.c_longlong)]
 
 
+FSQ_MAX_LEVELS = 11
+
+
+class FsqLevels(C.Structure):
+    """lvt_fsq_levels (include/lvt_hip.h): the level table of the FSQ kernels, passed by value."""
+    _fields_ = [("d", C.c_int), ("levels", C.c_int * FSQ_MAX_LEVELS)]
+
+
 CLIP_RECORD_BYTES = 16      # lvt_clip_record: float norm, float coef, int skip, int reserved
 
 
@@ -255,6 +263,9 @@ def _declare(lib):
         "lvt_dropout_bwd": (ci, [vp, cll, C.c_ulonglong, C.c_uint, C.c_uint, C.c_uint, cf, vp, vp, vp]),
         "lvt_l2norm_groups_fwd": (ci, [vp, cll, ci, ci, cf, vp, vp, vp, vp]),
         "lvt_l2norm_groups_bwd": (ci, [vp, vp, vp, cll, ci, ci, cf, vp, vp, vp]),
+        "lvt_fsq_fwd": (ci, [vp, cll, ci, ci, FsqLevels, ci, vp, vp, vp, vp]),
+        "lvt_fsq_bwd": (ci, [vp, vp, cll, ci, ci, FsqLevels, vp, vp, vp]),
+        "lvt_fsq_decode": (ci, [vp, cll, ci, ci, FsqLevels, ci, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)

@@ -5,7 +5,10 @@ EMA update, z_q_bar from the post-update codebook) -> ResDecoder -> x_tilde;
 losses: lambda * mse(x_tilde, x)  and  beta * mse(z_e, sg(z_q_bar)).
 With MODEL.CODEBOOK.COSINE the quantiser and the commitment loss see u = z_e with every sub-vector l2-normalised instead of z_e
 (lvt_amd/modeling/vq/cosine.py).
+With MODEL.CODEBOOK.FSQ.LEVELS the quantiser is FSQEmbedding: two trained projections around a fixed rounding rule, no codebook
+state and no quantiser loss terms (lvt_amd/modeling/vq/fsq.py).
 """
+import math
 import os
 
 from ...hip import ew
@@ -13,7 +16,8 @@ from ...solver import build_lr_scheduler, build_optimizer
 from ...utils.checkpoint import Checkpointer
 from ..loss import ReconstructionLoss
 from ..loss.loss import mse
-from ..vq import DVQEmbedding, SingleVQEmbedding
+from ..vq import DVQEmbedding, FSQEmbedding, SingleVQEmbedding
+from ..vq import fsq as fsq_rule
 from .ae import AutoEncoderModel
 from .build import META_ARCH_REGISTRY
 
@@ -24,8 +28,11 @@ class VQVAEModel(AutoEncoderModel):
         super().__init__(cfg)
         cb = cfg.MODEL.CODEBOOK
         self.use_codebook_ema = cb.EMA
+        self.fsq = bool(len(cb.FSQ.LEVELS))
         # (COSINE with EMA False is the quantisers' ValueError: a trained cosine codebook is not built)
-        if cb.NUM == 1:          # the default of the config tree: `VQEmbedding` used directly (vqvae.py:25-27)
+        if self.fsq:
+            self.codebook = self._build_fsq(cfg)
+        elif cb.NUM == 1:          # the default of the config tree: `VQEmbedding` used directly (vqvae.py:25-27)
             self.codebook = SingleVQEmbedding(cb.SIZE, cb.DIM, self.use_codebook_ema, cosine=cb.COSINE)
         else:
             self.codebook = DVQEmbedding(cb.NUM, cb.SIZE, cb.DIM, self.use_codebook_ema, cosine=cb.COSINE)
@@ -38,6 +45,25 @@ class VQVAEModel(AutoEncoderModel):
         self.pixel_loss = self.reconstruction_loss.pixel_loss
         self.beta = cb.BETA
         self.to(self.device)
+
+    def _build_fsq(self, cfg):
+        """FSQEmbedding from MODEL.CODEBOOK.FSQ.LEVELS, or the ValueError that names the keys at odds with it."""
+        cb = cfg.MODEL.CODEBOOK
+        levels = fsq_rule.check_levels(cb.FSQ.LEVELS)
+        if cb.SIZE != math.prod(levels):
+            raise ValueError("MODEL.CODEBOOK.SIZE (%r) must equal prod(MODEL.CODEBOOK.FSQ.LEVELS) = %d"
+                             % (cb.SIZE, math.prod(levels)))
+        if cb.EMA:
+            raise ValueError("MODEL.CODEBOOK.FSQ.LEVELS trains its two projections by gradient and keeps no EMA state: set "
+                             "MODEL.CODEBOOK.EMA to False (Base-VQVAE.yaml sets it to True)")
+        if cb.COSINE:
+            raise ValueError("MODEL.CODEBOOK.FSQ.LEVELS has no learned codebook to search on the unit sphere: set "
+                             "MODEL.CODEBOOK.COSINE to False")
+        if cb.RESTART.ENABLED:
+            raise ValueError("MODEL.CODEBOOK.FSQ.LEVELS has no codes that can die: set MODEL.CODEBOOK.RESTART.ENABLED to False")
+        codebook = FSQEmbedding(cb.NUM, levels, cb.DIM)
+        self.init_weights(codebook, cfg.MODEL.INIT_TYPE)
+        return codebook
 
     def train(self, mode=True):
         super().train(mode)
@@ -91,6 +117,11 @@ class VQVAEModel(AutoEncoderModel):
         return self.generator.forward_cl(self.codebook.embed_cl(latent))
 
     def _supervised_loss_cl(self, x, return_x=False):
+        if self.fsq:
+            # the quantiser is a function of z_e and its two projections: the reconstruction loss trains all of it
+            x_tilde = self.generator.forward_cl(self.codebook.straight_through_cl(self.encoder.forward_cl(x), defer=True))
+            loss = self.reconstruction_loss(x_tilde, x, denom=x.numel() // x.shape[-1] * len(self.cfg.MODEL.PIXEL_MEAN))
+            return (loss, x, x_tilde) if return_x else loss
         # (COSINE: u, the l2-normalised sub-vectors, takes the place of z_e from here on; the identity when the key is off)
         z_e = self.codebook.normalise_cl(self.encoder.forward_cl(x))
         # the decoder needs z_q_st only (pre-update codebook): the all-reduce of the EMA statistics that the quantiser
