@@ -117,11 +117,6 @@ class VQVAEModel(AutoEncoderModel):
         return self.generator.forward_cl(self.codebook.embed_cl(latent))
 
     def _supervised_loss_cl(self, x, return_x=False):
-        if self.fsq:
-            # the quantiser is a function of z_e and its two projections: the reconstruction loss trains all of it
-            x_tilde = self.generator.forward_cl(self.codebook.straight_through_cl(self.encoder.forward_cl(x), defer=True))
-            loss = self.reconstruction_loss(x_tilde, x, denom=x.numel() // x.shape[-1] * len(self.cfg.MODEL.PIXEL_MEAN))
-            return (loss, x, x_tilde) if return_x else loss
         # (COSINE: u, the l2-normalised sub-vectors, takes the place of z_e from here on; the identity when the key is off)
         z_e = self.codebook.normalise_cl(self.encoder.forward_cl(x))
         # the decoder needs z_q_st only (pre-update codebook): the all-reduce of the EMA statistics that the quantiser
@@ -135,10 +130,12 @@ class VQVAEModel(AutoEncoderModel):
         z_q_bar = self.codebook.finish_ema()
         c = len(self.cfg.MODEL.PIXEL_MEAN)
         loss = self.reconstruction_loss(x_tilde, x, denom=x.numel() // x.shape[-1] * c)
-        loss["loss_commitment"] = mse(z_e, z_q_bar.detach(), scale=self.beta)
-        if not self.use_codebook_ema:
-            # vector-quantisation objective of a TRAINED codebook, under the reference's key (vqvae.py:83-84)
-            loss["loss_dict"] = mse(z_q_bar, z_e.detach())
+        if z_q_bar is not None:
+            # (FSQ has none: it is a function of z_e and its two projections, and the reconstruction loss trains all of it)
+            loss["loss_commitment"] = mse(z_e, z_q_bar.detach(), scale=self.beta)
+            if not self.use_codebook_ema:
+                # vector-quantisation objective of a TRAINED codebook, under the reference's key (vqvae.py:83-84)
+                loss["loss_dict"] = mse(z_q_bar, z_e.detach())
         return (loss, x, x_tilde) if return_x else loss
 
     def _generator_loss_cl(self, x):

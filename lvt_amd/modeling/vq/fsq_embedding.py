@@ -13,8 +13,8 @@ from torch import nn
 from ...hip import binding as L
 from ...hip import fsq as K
 from ...hip import gemm as G
-from .. import convstack
 from . import fsq as rule
+from .vq_embedding import Quantiser
 
 
 def _rows4(t, rows):
@@ -71,12 +71,10 @@ class _FSQFn(torch.autograd.Function):
         return dz, dwi, dbi, dwo, dbo, None, None
 
 
-class FSQEmbedding(nn.Module):
+class FSQEmbedding(Quantiser):
     """FSQEmbedding(num, levels, dim): `num` code channels of prod(levels) codes each over `dim` encoder / decoder channels.
-    Parameters proj_in (dim -> num * d) and proj_out (num * d -> dim); no buffers.  Offers what VQVAEModel calls on a quantiser;
-    train and eval mode are the same function."""
-
-    ema = cosine = restart_enabled = False
+    Parameters proj_in (dim -> num * d) and proj_out (num * d -> dim); no buffers.  A `Quantiser` (vq_embedding.py) with nothing
+    to normalise, update or restart; train and eval mode are the same function."""
 
     def __init__(self, num, levels, dim):
         super().__init__()
@@ -121,13 +119,7 @@ class FSQEmbedding(nn.Module):
         """The tensors a data-parallel run broadcasts from rank 0 (meta_arch/vqvae.py wrap_parallel)."""
         return (self.proj_in.weight.data, self.proj_in.bias.data, self.proj_out.weight.data, self.proj_out.bias.data)
 
-    def health_scalars(self):
-        return None                                       # (no health record on the device: every code exists by construction)
-
-    # ---- channels-last fast paths (the interface VQVAEModel uses: see DVQEmbedding) ---------------------------------------
-    def normalise_cl(self, z_cl):
-        return z_cl
-
+    # ---- channels-last fast paths (the interface VQVAEModel uses: see CodebookQuantiser) ----------------------------------
     def _rows(self, z_cl):
         n, _, h, w, d = z_cl.shape
         L.require(z_cl)
@@ -144,12 +136,19 @@ class FSQEmbedding(nn.Module):
 
     def straight_through_cl(self, z_cl, defer=False):
         """(N,1,H,W,D) -> z_out channels-last, what the decoder receives, with the straight-through graph to z_cl and the two
-        projections.  defer=False returns the pair (z_out, z_out), the shape of the other quantisers' (z_q_st, z_q_bar)."""
+        projections.  defer=False returns the pair (z_out, z_out), the shape of the other quantisers' (z_q_st, z_q_bar);
+        after defer=True there is nothing to finish: no z_q_bar, hence no quantiser loss terms."""
         n, h, w, z2d = self._rows(z_cl)
         out, idx = _FSQFn.apply(z2d, self.proj_in.weight, self.proj_in.bias, self.proj_out.weight, self.proj_out.bias, self, h * w)
         self.last_indices = idx.view(n, self.num, h, w)      # kept for evaluators / tests
         out = out.view(n, 1, h, w, self.D)
         return out if defer else (out, out)
+
+    def finish_ema(self):
+        return None
+
+    def abandon_ema(self):
+        pass
 
     def embed_cl(self, latents):
         """(N,num,H,W) int64 -> (N,1,H,W,D) channels-last."""
@@ -160,16 +159,3 @@ class FSQEmbedding(nn.Module):
         z_q = K.fsq_decode(latents.contiguous().view(n, num, h * w), self.levels, self.width)
         _, _, wo = self._operands()
         return self._project_out(z_q, wo, self.proj_out.bias.detach()).view(n, 1, h, w, self.D)
-
-    # ---- the quantisers' call contract (vq_embedding.py) ---------------------------------------------------------------------
-    def forward(self, z_e_x, mode=""):
-        if mode == "":
-            assert z_e_x.dim() == 4
-            return self.indices_cl(convstack._LayoutIn.apply(z_e_x))
-        if mode == "st":
-            assert z_e_x.dim() == 4
-            st = convstack._LayoutOut.apply(self.straight_through_cl(convstack._LayoutIn.apply(z_e_x), defer=True), self.D)
-            return st, st
-        if mode == "emb":
-            return self.embed_cl(z_e_x).squeeze(1)       # (N,H,W,D)
-        raise ValueError
